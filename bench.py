@@ -224,6 +224,43 @@ def plan_chunks(k):
     return c, even // c, k % 2
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs: bytes of array data written at most, all ranks together
+DUMP_SAMPLE_SEED = 20240601    # ... the fixed sample of envs taken when the full outputs would be more
+
+
+def last_step_outputs(vec, rollout=None):
+    """What a caller of the timed path holds after its last step, on the host, env-major: the env step's (observation, reward,
+    done) -- the observation gathered dense out of a row log -- and, for the rollout loop, the last step's slice of every
+    rollout buffer plus the head's outputs for the observation after it (`next_values` is the rollout's last_value)."""
+    m, n = vec._mem, vec.num_envs
+    out = {"obs": m.to_host(vec.obs_dense()).reshape((n,) + tuple(vec.obs_shape)), "reward": m.to_host(vec._rew),
+           "done": m.to_host(vec._done)}
+    if rollout is not None:
+        for k, t in rollout.buf.items():
+            out["rollout_" + k] = m.to_host(t[-1])
+        for k, t in rollout.cur.items():
+            out["next_" + k] = m.to_host(t)
+    return out
+
+
+def dump_outputs(outdir, arrays, first, budget, suffix=""):
+    """Writes every array (axis 0 = env) as <outdir>/<name><suffix>.npy -- float64 stays float64, anything else becomes
+    float32 -- plus env_index<suffix>.npy, the global env ids of the rows.  When all of it would exceed `budget` bytes, the
+    rows of a fixed, seeded sample of the envs are written instead (the same sample for every array and every run)."""
+    import numpy as np
+    conv = {k: np.asarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32) for k, a in arrays.items()}
+    n = min(len(a) for a in conv.values())
+    per_env = 8 + sum(a[:1].nbytes for a in conv.values())
+    rows = np.arange(n)
+    if n * per_env > budget:
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, max(1, budget // per_env), replace=False))
+    conv["env_index"] = (first + rows).astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in conv.items():
+        np.save(os.path.join(outdir, k + suffix + ".npy"), a if k == "env_index" else a[rows])
+    return {"dir": outdir, "arrays": sorted(k + suffix for k in conv), "envs": int(len(rows)), "of_envs": int(n)}
+
+
 def spawn_ranks(args, argv):
     """--gpus N without a launcher: start N ranks (one per GPU) before this process touches the GPU; relay rank 0's line."""
     import socket
@@ -278,6 +315,12 @@ def main():
     ap.add_argument("--emulate-steps-max", type=int, default=0,
                     help="TEST ONLY (with --emulate): episode time limit, so that episodes end inside a dry run and the success "
                          "all-gather + curriculum rule have something to agree on")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what their last step computed (observation, reward, done; with the rollout "
+                         "loop also the rollout buffers' last slice and the head's next outputs) as DIR/<name>.npy, float32 / "
+                         "float64, at most {} MB in all (a fixed, seeded sample of the envs beyond that); the inputs are the same "
+                         "from run to run, so two builds can be compared output for output.  With N ranks: <name>_rank<r>.npy".format(
+                             DUMP_BYTES >> 20))
     args = ap.parse_args()
 
     world_env = os.environ.get("WORLD_SIZE")
@@ -548,6 +591,10 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         wall = float(tt.item())
     event_ms = ev0.elapsed_time(ev1) / args.steps if not args.emulate else None
+    dumped = None
+    if args.dump_outputs:   # (outside the clock, before any side measurement steps the env on)
+        dumped = dump_outputs(args.dump_outputs, last_step_outputs(vec, get_rollout(chunk) if fused and chunk else None), first,
+                              DUMP_BYTES // world, "_rank{}".format(rank) if world > 1 else "")
 
     # ---- side measurements (same launches, other regimes / consumers / configurations); never part of `value`
     sides = {}
@@ -840,6 +887,8 @@ def main():
                          "clock": "wall clock of the timed region (the same interval as `value`)",
                          "algorithmic_bytes_per_env_step": ALG_BYTES[args.workload], "source_hash": source_hash()},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         for k, v in sides.items():
             if traffic and isinstance(v, dict) and "ms_per_step" in v and k in ("steady_state",):
                 v["measured_GBs"] = traffic / (v["ms_per_step"] * 1e-3) / 1e9

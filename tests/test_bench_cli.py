@@ -113,3 +113,43 @@ def test_eight_ranks_of_configs3_dry_run():
     assert out["emulated_episodes_seen"] >= 262144          # 3-step episodes: every env finished at least one, counted over ALL ranks
     lv = out["emulated_curriculum_levels"]
     assert len(lv) == 8 and len(set(lv)) == 1, lv
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed -- observation, reward, done and the env ids of the rows -- as
+    float32 / float64 .npy files within 64 MB; the same arguments give the same inputs and so the same files, and --steps sets
+    the number of timed steps (a run one step longer ends on another state)."""
+    import numpy as np
+    runs = {}
+    for tag, steps in (("a", 6), ("b", 6), ("c", 7)):
+        d = tmp_path / tag
+        p, out = _bench("--emulate", "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline", "--dump-outputs", str(d))
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert out["steps"] == steps and out["ms_per_step"] > 0
+        assert out["dumped_outputs"]["envs"] == out["dumped_outputs"]["of_envs"] == out["config"]["envs_per_gpu"]
+        runs[tag] = {f[:-len(".npy")]: np.load(str(d / f)) for f in os.listdir(str(d))}
+        assert sorted(runs[tag]) == out["dumped_outputs"]["arrays"]
+    a, b, c = runs["a"], runs["b"], runs["c"]
+    assert {"obs", "reward", "done", "env_index"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64e6
+    n = len(a["env_index"])
+    for k, x in a.items():
+        assert x.dtype in (np.float32, np.float64) and len(x) == n, (k, x.dtype, x.shape)
+        assert np.array_equal(x, b[k], equal_nan=True), k
+    assert np.array_equal(a["env_index"], np.arange(n)) and set(np.unique(a["done"])) <= {0.0, 1.0}
+    assert np.isfinite(a["obs"]).all() and not np.array_equal(a["obs"], c["obs"])
+
+
+def test_dump_outputs_sample_a_fixed_subset_beyond_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    arrays = {"obs": np.arange(1000 * 6, dtype=np.float32).reshape(1000, 2, 3), "done": np.arange(1000, dtype=np.uint8)}
+    got = bench.dump_outputs(str(tmp_path / "x"), arrays, 5000, budget=100 * 36)
+    again = bench.dump_outputs(str(tmp_path / "y"), arrays, 5000, budget=100 * 36)
+    assert got["envs"] == again["envs"] == 100 and got["of_envs"] == 1000
+    idx = np.load(str(tmp_path / "x" / "env_index.npy"))
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(str(tmp_path / "y" / "env_index.npy")))
+    rows = (idx - 5000).astype(np.int64)
+    assert np.array_equal(np.load(str(tmp_path / "x" / "obs.npy")), arrays["obs"][rows])
+    assert np.load(str(tmp_path / "x" / "done.npy")).dtype == np.float32

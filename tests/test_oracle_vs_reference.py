@@ -1,60 +1,72 @@
-"""Build-container-only check: the restated gym oracle equals the VERBATIM reference module step by step (float64),
-for the shipped config variants and the feature switches, with the reference's own MT19937 consumption order.
-Skipped where /root/reference is not mounted (GPU box) -- there the committed golden vectors pin the oracle."""
+"""The restated gym oracle equals the VERBATIM reference module step by step (float64), for the shipped config variants and
+the feature switches, with the reference's own MT19937 consumption order -- against the reference's outputs recorded in
+tests/golden/ref_traces_mt19937.npz (tests/golden/make_reference_traces.py: the same seed, actions and auto-resets)."""
 import copy
+import json
+import os
 
 import numpy as np
 import pytest
 
 import configs
-from golden._ref_harness import load_reference
+from golden import make_reference_traces as mrt
 from oracle.gym_restated import FixedWingOracle
 
-ref = load_reference()
-pytestmark = pytest.mark.skipif(ref is None, reason="reference not mounted")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-def _cmp(a, b, path=""):
-    if isinstance(a, dict):
-        assert set(a.keys()) == set(b.keys()), (path, a.keys(), b.keys())
-        return max([_cmp(a[k], b[k], path + "/" + str(k)) for k in a] + [0])
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (path, a.shape, b.shape)
-    assert np.array_equal(np.isnan(a), np.isnan(b)), (path, a, b)
-    return float(np.max(np.abs(np.where(np.isnan(a), 0, a - b)))) if a.size else 0.0
+def _cmp(leaves, schema, values, path):
+    """Worst |ours - recorded| over one event; the key paths, shapes and NaN positions must agree."""
+    got = {p: v for p, v in leaves}
+    want = {p: s for p, s in schema}
+    assert set(got) == set(want), (path, sorted(set(got) ^ set(want)))
+    worst, off = 0.0, 0
+    for p, shape in schema:
+        if shape is None:
+            assert got[p] is None, (path, p, "a dict in the reference")
+            continue
+        a = got[p]
+        assert a is not None and list(a.shape) == shape, (path, p, None if a is None else a.shape, shape)
+        b = values[off:off + a.size].reshape(a.shape)
+        off += a.size
+        assert np.array_equal(np.isnan(a), np.isnan(b)), (path, p, a, b)
+        if a.size:
+            worst = max(worst, float(np.max(np.abs(np.where(np.isnan(a), 0, a - b)))))
+    return worst, off
 
 
-CASES = [c for c in configs.CASES if c[0] not in ("spec_c3",)] + configs.ORACLE_ONLY_CASES
+CASES = mrt.CASES
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
-def test_restated_gym_equals_verbatim_reference(case, tmp_path):
-    import json
+def test_restated_gym_equals_verbatim_reference(case):
     name, kind, ckw, skw = case
-    cfg = configs.reference_like(kind)
-    path = str(tmp_path / "cfg.json")
-    with open(path, "w") as f:
-        json.dump(cfg, f)
-    e1 = ref.FixedWingAircraft(path, config_kw=copy.deepcopy(ckw), sim_config_kw=copy.deepcopy(skw))
-    e2 = FixedWingOracle(cfg, config_kw=copy.deepcopy(ckw), sim_config_kw=copy.deepcopy(skw))
-    e1.seed(3)
-    e2.seed(3)
-    worst = _cmp(e1.reset(), e2.reset(), "reset")
-    rng = np.random.default_rng(1)
-    a = rng.uniform(-1, 1, 3)
+    with np.load(os.path.join(GOLDEN, "ref_traces_mt19937.npz"), allow_pickle=False) as z:
+        layout = json.loads(str(z[name + ":layout"]))
+        values = z[name + ":values"]
+    assert layout["seed"] == mrt.SEED and layout["steps"] == mrt.STEPS
+    events = iter(layout["events"])
+    pos = [0]
+
+    def check(kind_, leaves, done=False, termination=None, t=None):
+        ev_kind, schema_id, ev_done, ev_term = next(events)
+        assert ev_kind == kind_, (t, ev_kind, kind_)
+        assert done == ev_done and termination == ev_term, (t, done, ev_done, termination, ev_term)
+        w, n = _cmp(leaves, layout["schemas"][schema_id], values[pos[0]:], (kind_, t))
+        pos[0] += n
+        return w
+
+    env = FixedWingOracle(configs.reference_like(kind), config_kw=copy.deepcopy(ckw), sim_config_kw=copy.deepcopy(skw))
+    env.seed(mrt.SEED)
+    worst = check("reset", mrt.event_leaves("reset", env.reset()))
     episodes = 0
-    for t in range(260):
-        if rng.uniform() < 0.3:
-            a = np.clip(a + rng.normal(0, 0.4, 3), -1.8, 1.8)
-        o1, r1, d1, i1 = e1.step(a.copy())
-        o2, r2, d2, i2 = e2.step(a.copy())
-        assert d1 == d2 and i1.get("termination") == i2.get("termination"), t
-        worst = max(worst, _cmp(o1, o2, "obs"), _cmp(r1, r2, "reward"))
-        worst = max(worst, _cmp({k: v for k, v in i1.items() if k != "termination"},
-                                {k: v for k, v in i2.items() if k != "termination"}, "info"))
-        if d1:
+    for t, a in enumerate(mrt.actions()):
+        o, r, d, i = env.step(a.copy())
+        worst = max(worst, check("step", mrt.event_leaves("step", o, r, i), bool(d), i.get("termination"), t))
+        if d:
             episodes += 1
-            worst = max(worst, _cmp(e1.reset(), e2.reset(), "reset"))
+            worst = max(worst, check("reset", mrt.event_leaves("reset", env.reset()), t=t))
+    assert next(events, None) is None and pos[0] == values.size   # every recorded event replayed
     assert worst < 1e-9, worst
 
 
@@ -65,8 +77,7 @@ INERT = {
                   "action.scale_low": "as scale_high"}, "-": {}},
     "cnn": {"+": {}, "-": {"action.bounds_outside_cost": "never read by fixed_wing.py (grep: no occurrence)"}},
 }
-SHIPPED = {"default": "fixed_wing_config.json", "dev": "fixed_wing_config_dev.json", "examples": "examples/fixed_wing_config.json",
-           "mlp": "examples/models/mlp_controller/fixed_wing_config.json", "cnn": "examples/models/cnn_controller/fixed_wing_config.json"}
+SHIPPED = mrt.SHIPPED   # (kind -> the file's path in the reference; the files themselves: tests/golden/ref_shipped_configs.json)
 
 
 def _flat(d, prefix=""):
@@ -86,11 +97,11 @@ def _flat(d, prefix=""):
 def test_preset_equals_the_shipped_configuration_file(kind):
     """presets.preset(kind) -- what the kernels are frozen for and what every test calls 'the reference's configuration' -- is
     the file the reference ships, key by key and value by value, modulo the stated inert keys."""
-    import json
-    import os
     from gym_fixed_wing import presets
-    with open(os.path.join("/root/reference/gym_fixed_wing", SHIPPED[kind])) as f:
-        shipped = _flat(json.load(f))
+    with open(os.path.join(GOLDEN, "ref_shipped_configs.json")) as f:
+        recorded = json.load(f)
+    assert recorded["configs"][kind]["file"] == SHIPPED[kind]
+    shipped = _flat(recorded["configs"][kind]["config"])
     ours = _flat({k: v for k, v in presets.preset(kind).items() if k != "_comment"})
     extra = {k: v for k, v in ours.items() if k not in shipped}
     missing = {k: v for k, v in shipped.items() if k not in ours}
@@ -101,5 +112,4 @@ def test_preset_equals_the_shipped_configuration_file(kind):
     assert not differ, differ
     # the inert keys really are: the reference module never reads `bounds_outside_cost`
     if kind == "cnn":
-        with open("/root/reference/gym_fixed_wing/fixed_wing.py") as f:
-            assert "bounds_outside_cost" not in f.read()
+        assert recorded["module_mentions"]["bounds_outside_cost"] is False
