@@ -2,7 +2,7 @@
 """Train a PPO attitude controller on the MI355X-native env -- the reference's examples/train_rl_controller.py
 (`VecNormalize(SubprocVecEnv(...))` + `PPO2(MlpPolicy, env).learn(5e6, callback=monitor_training)` with the curriculum rule of
 its callback, :80-87) with the whole data path on the device: rollouts by the HIP head + env step kernels, advantages by fwg_gae,
-the PPO2 update in torch on the same buffers, the success sums all-gathered over RCCL, the curriculum raised on every rank.
+the PPO2 update in torch on the same buffers (or, with --update hip, as HIP kernels: gym_fixed_wing/learner.py), the success sums all-gathered over RCCL, the curriculum raised on every rank.
 
     python examples/train_ppo.py --envs 4096 --timesteps 100e6 --out model.npz
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_ppo.py --envs 32768
@@ -30,14 +30,14 @@ from gym_fixed_wing.ppo import PPO  # noqa: E402
 
 
 def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, learning_rate=5e-4, n_steps=128, curriculum=True,
-          config="examples", log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None):
+          config="examples", log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch"):
     vec = make_sharded_env(presets.preset(config), total_envs=envs, rank=rank, world_size=world, device=local, derived_views=False,
                            seed=seed)
     sched = CurriculumSchedule(level=0.25 if curriculum else 1.0)     # (train_rl_controller.py:162: curriculum_level = 0.25)
     vec.set_curriculum_level(sched.level)
     vec.reset()
     ppo = PPO(vec, seed=seed, curriculum=sched, n_steps=n_steps, nminibatches=nminibatches, noptepochs=noptepochs,
-              learning_rate=learning_rate, fused=fused, ent_coef=ent_coef)
+              learning_rate=learning_rate, fused=fused, ent_coef=ent_coef, update=update)
     t0 = time.perf_counter()
     window = []    # success over the last finished episodes (the reference's ep_info_buf holds the last 100)
 
@@ -68,6 +68,7 @@ def main():
     ap.add_argument("--lr", type=float, default=5e-4)
     ap.add_argument("--ent-coef", type=float, default=0.01)
     ap.add_argument("--disable-curriculum", action="store_true")
+    ap.add_argument("--update", choices=("torch", "hip"), default="torch", help="PPO update: torch autograd (default) or the HIP kernels")
     ap.add_argument("--out", default=None, help="save weights + VecNormalize statistics (.npz)")
     ap.add_argument("--curve", default=None, help="write the learning curve (JSON)")
     args = ap.parse_args()
@@ -77,7 +78,7 @@ def main():
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
     torch.cuda.set_device(local)
     ppo, res = train(args.envs, args.timesteps, args.seed, args.nminibatches, args.noptepochs, args.lr, curriculum=not args.disable_curriculum,
-                     rank=rank, world=world, local=local, ent_coef=args.ent_coef)
+                     rank=rank, world=world, local=local, ent_coef=args.ent_coef, update=args.update)
     if rank == 0:
         print("{:.3e} env-steps in {:.1f} s = {:.3e} env-steps/s INCLUDING the optimiser ({} updates)".format(
             ppo.num_timesteps, res["seconds"], res["env_steps_per_s"], res["updates"]))

@@ -18,6 +18,7 @@
 #include <vector>
 #include "fwgym_env.h"
 #include "fwgym_actor.h"   // the rollout head (k_rollout below runs it in the same launch as the env step)
+#include "fwgym_learner.h" // the PPO update on the device (fwg_ppo_*)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
@@ -2782,6 +2783,114 @@ int fwg_rollout_step(fwg_handle* h, fwg_actor* a, float* norm_obs_out, float* ac
     }
     HIP_TRY(hipGetLastError());
     h->gstep += 1;
+    return FWG_OK;
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// PPO update (include/fwgym.h "PPO update"): kernels in fwgym_learner.h
+// =====================================================================================================================
+struct fwg_learner {
+    fwg_actor* head;
+    PpoLayout L;
+    float* d_slab;     // [FWG_PPO_MAX_BLOCKS][SW] partial gradients of fwg_ppo_grad
+    float* d_grad;     // [P + FWG_PPO_NSTAT] flat gradient of fwg_ppo_step
+};
+
+static PpoBatch ppo_batch(const fwg_ppo_batch* b) {
+    PpoBatch B;
+    B.obs = b->obs; B.act = b->actions; B.val = b->values; B.logp = b->logp; B.adv = b->adv; B.ret = b->returns;
+    return B;
+}
+static bool ppo_batch_ok(const fwg_ppo_batch* b) {
+    return b && b->obs && b->actions && b->values && b->logp && b->adv && b->returns;
+}
+static int ppo_launch_grad(fwg_learner* L, const fwg_ppo_batch* b, const int64_t* idx, int64_t mb, const float* moments,
+                           const float* params, const fwg_ppo_hparams* hp, float* grad_out, hipStream_t st) {
+    PpoGradArgs G;
+    G.B = ppo_batch(b); G.idx = (const long long*)idx; G.mb = (long)mb; G.mom = moments; G.params = params;
+    G.hp = (const PpoHparams*)hp; G.slab = L->d_slab; G.L = L->L;
+    G.ntiles = (long)((mb + FWG_PPO_ROWS - 1) / FWG_PPO_ROWS);
+    const unsigned nb = (unsigned)(G.ntiles < FWG_PPO_MAX_BLOCKS ? G.ntiles : FWG_PPO_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_ppo_grad, dim3(nb), dim3(FWG_PPO_THREADS), (size_t)ppo_grad_lds_floats() * sizeof(float), st, G);
+    HIP_TRY(hipGetLastError());
+    const int n = L->L.P + FWG_PPO_NSTAT;
+    hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((n + FWG_PPO_THREADS - 1) / FWG_PPO_THREADS)), dim3(FWG_PPO_THREADS), 0, st,
+                       (const float*)L->d_slab, (int)nb, L->L, (const PpoHparams*)hp, grad_out);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+extern "C" {
+
+int fwg_learner_create(fwg_actor* head, fwg_learner** out) {
+    if (!head || !out) return fail_with(FWG_ERR_INVALID, "fwg_learner_create: null argument");
+    HIP_TRY(hipSetDevice(head->device));
+    fwg_learner* L = new fwg_learner();
+    L->head = head;
+    L->L = ppo_layout(head->D, head->act_dim);
+    HIP_TRY(hipMalloc((void**)&L->d_slab, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&L->d_grad, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
+    HIP_TRY(hipMemset(L->d_slab, 0, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
+    HIP_TRY(hipMemset(L->d_grad, 0, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
+    // (more than 64 KiB of dynamic LDS: asked for here, never inside a capture)
+    HIP_TRY(hipFuncSetAttribute((const void*)k_ppo_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ppo_grad_lds_floats() * sizeof(float))));
+    *out = L;
+    return FWG_OK;
+}
+
+void fwg_learner_destroy(fwg_learner* L) {
+    if (!L) return;
+    (void)hipFree(L->d_slab); (void)hipFree(L->d_grad);
+    delete L;
+}
+
+int64_t fwg_learner_num_params(const fwg_learner* L) { return L ? (int64_t)L->L.P : -1; }
+
+int fwg_ppo_moments(fwg_learner* L, const float* adv, const int64_t* perm, int64_t mb, int n_minibatches, float* moments, void* stream) {
+    if (!L || !adv || !perm || !moments) return fail_with(FWG_ERR_INVALID, "fwg_ppo_moments: null argument");
+    if (mb < 1 || n_minibatches < 1) return fail_with(FWG_ERR_INVALID, "fwg_ppo_moments: mb and n_minibatches must be positive");
+    hipLaunchKernelGGL(k_ppo_moments, dim3((unsigned)n_minibatches), dim3(FWG_PPO_THREADS), FWG_PPO_THREADS * sizeof(double), (hipStream_t)stream,
+                       adv, (const long long*)perm, (long)mb, moments);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_ppo_grad(fwg_learner* L, const fwg_ppo_batch* b, const int64_t* idx, int64_t mb, const float* moments, const float* params,
+                 const fwg_ppo_hparams* hp, float* grad_out, void* stream) {
+    if (!L || !ppo_batch_ok(b) || !idx || !moments || !params || !hp || !grad_out) return fail_with(FWG_ERR_INVALID, "fwg_ppo_grad: null argument");
+    if (mb < 1) return fail_with(FWG_ERR_INVALID, "fwg_ppo_grad: mb must be positive");
+    return ppo_launch_grad(L, b, idx, mb, moments, params, hp, grad_out, (hipStream_t)stream);
+}
+
+int fwg_ppo_apply(fwg_learner* L, const float* grad, int64_t mb, const fwg_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
+                  int32_t* step, float* stats_acc, void* stream) {
+    if (!L || !grad || !hp || !params || !adam_m || !adam_v || !step || !stats_acc) return fail_with(FWG_ERR_INVALID, "fwg_ppo_apply: null argument");
+    if (mb < 1) return fail_with(FWG_ERR_INVALID, "fwg_ppo_apply: mb must be positive");
+    hipLaunchKernelGGL(k_ppo_apply, dim3(1), dim3(FWG_PPO_APPLY_THREADS), FWG_PPO_APPLY_THREADS * sizeof(float), (hipStream_t)stream,
+                       grad, (long)mb, L->L, (const PpoHparams*)hp, params, adam_m, adam_v, (int*)step, stats_acc);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_ppo_step(fwg_learner* L, const fwg_ppo_batch* b, const int64_t* idx, int64_t mb, const float* moments, const fwg_ppo_hparams* hp,
+                 float* params, float* adam_m, float* adam_v, int32_t* step, float* stats_acc, void* stream) {
+    if (!L || !ppo_batch_ok(b) || !idx || !moments || !hp || !params || !adam_m || !adam_v || !step || !stats_acc)
+        return fail_with(FWG_ERR_INVALID, "fwg_ppo_step: null argument");
+    if (mb < 1) return fail_with(FWG_ERR_INVALID, "fwg_ppo_step: mb must be positive");
+    const int rc = ppo_launch_grad(L, b, idx, mb, moments, params, hp, L->d_grad, (hipStream_t)stream);
+    if (rc != FWG_OK) return rc;
+    return fwg_ppo_apply(L, L->d_grad, mb, hp, params, adam_m, adam_v, step, stats_acc, stream);
+}
+
+int fwg_actor_pack(fwg_learner* L, const float* params, void* stream) {
+    if (!L || !params) return fail_with(FWG_ERR_INVALID, "fwg_actor_pack: null argument");
+    const fwg_actor* a = L->head;
+    const int n = 2 * actor_frags(a->nk1) * 64 + 2 * FWG_ACT_BIAS_FLOATS + FWG_ACT_MAX_ACT;
+    hipLaunchKernelGGL(k_actor_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, L->L, a->nk1,
+                       a->d_frags, a->d_bias, a->d_log_std);
+    HIP_TRY(hipGetLastError());
     return FWG_OK;
 }
 

@@ -3,7 +3,7 @@ module without a built library raises, there is no CPU fallback."""
 import ctypes as C
 import os
 
-FWG_ABI_VERSION = 20
+FWG_ABI_VERSION = 21
 N_VARS = 23
 N_RESET_VARS = 21
 N_PARAMS = 49
@@ -139,6 +139,19 @@ class ActorStats(C.Structure):
                 ("ret_mean", C.c_float), ("ret_var", C.c_float), ("ret_count", C.c_float)]
 
 
+class PpoHparams(C.Structure):
+    """fwg_ppo_hparams: the update's hyper-parameters, read on the device at every launch."""
+    _fields_ = [(n, C.c_double) for n in ["lr", "cliprange", "ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps"]]
+
+
+class PpoBatch(C.Structure):
+    """fwg_ppo_batch: device pointers of the flattened rollout buffers."""
+    _fields_ = [(n, C.c_void_p) for n in ["obs", "actions", "values", "logp", "adv", "returns"]]
+
+
+PPO_NSTAT = 4   # loss sums appended to a gradient buffer (include/fwgym.h "PPO update")
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -155,7 +168,9 @@ EXPORTS = ["fwg_abi_version", "fwg_get_layout", "fwg_create", "fwg_destroy", "fw
            "fwg_capture_begin", "fwg_capture_end", "fwg_capture_parity", "fwg_replay_check", "fwg_finish_episodes", "fwg_actor_create", "fwg_actor_destroy", "fwg_actor_set_weights",
            "fwg_actor_set_stats", "fwg_actor_get_stats", "fwg_actor_configure", "fwg_actor_seed", "fwg_actor_observe",
            "fwg_actor_act", "fwg_attach_observer", "fwg_obs_log_floats", "fwg_obs_window", "fwg_reduce_success_device",
-           "fwg_obs_gather", "fwg_actor_set_obs_log", "fwg_selftest_philox", "fwg_rollout_available", "fwg_rollout_step", "fwg_gae"]
+           "fwg_obs_gather", "fwg_actor_set_obs_log", "fwg_selftest_philox", "fwg_rollout_available", "fwg_rollout_step", "fwg_gae",
+           "fwg_learner_create", "fwg_learner_destroy", "fwg_learner_num_params", "fwg_ppo_moments", "fwg_ppo_grad", "fwg_ppo_apply",
+           "fwg_ppo_step", "fwg_actor_pack"]
 _libs = {}
 
 
@@ -244,6 +259,19 @@ def load_library(path=None):
     lib.fwg_rollout_step.restype = C.c_int
     lib.fwg_gae.argtypes = [i64, i64, vp, vp, vp, vp, f32, f32, vp, vp, vp]
     lib.fwg_gae.restype = C.c_int
+    lib.fwg_learner_create.argtypes = [vp, C.POINTER(vp)]
+    lib.fwg_learner_create.restype = C.c_int
+    lib.fwg_learner_destroy.argtypes = [vp]
+    lib.fwg_learner_destroy.restype = None
+    lib.fwg_learner_num_params.argtypes = [vp]
+    lib.fwg_learner_num_params.restype = i64
+    lib.fwg_ppo_moments.argtypes = [vp, vp, vp, i64, C.c_int, vp, vp]
+    lib.fwg_ppo_grad.argtypes = [vp, C.POINTER(PpoBatch), vp, i64, vp, vp, vp, vp, vp]
+    lib.fwg_ppo_apply.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.fwg_ppo_step.argtypes = [vp, C.POINTER(PpoBatch), vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.fwg_actor_pack.argtypes = [vp, vp, vp]
+    for name in ("fwg_ppo_moments", "fwg_ppo_grad", "fwg_ppo_apply", "fwg_ppo_step", "fwg_actor_pack"):
+        getattr(lib, name).restype = C.c_int
     for name in ("fwg_actor_create", "fwg_actor_set_weights", "fwg_actor_set_stats", "fwg_actor_get_stats",
                  "fwg_actor_configure", "fwg_actor_seed", "fwg_actor_observe", "fwg_actor_act"):
         getattr(lib, name).restype = C.c_int

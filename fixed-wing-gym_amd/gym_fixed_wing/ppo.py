@@ -7,11 +7,14 @@ script does with `PPO2(MlpPolicy, VecNormalize(SubprocVecEnv(...))).learn(total_
   advantages  fwg_gae (HIP, one launch over the rollout buffers, 17 B per transition);
   update      the clipped-surrogate objective of stable-baselines' PPO2 with its defaults (gamma 0.99, lambda 0.95, clip 0.2 on
               policy AND value, entropy 0.01, value 0.5, lr 2.5e-4 Adam eps 1e-5, 4 epochs x 4 minibatches, gradient norm 0.5) --
-              torch autograd on the 12-64-64 networks (the model side is not the hot path);
+              torch autograd on the 12-64-64 networks by default; PPO(update="hip") runs it as HIP kernels instead
+              (learner.HipLearner: forward / backward on the matrix cores, clip and Adam on the device, one captured graph
+              per update, the head repacked on the device);
   curriculum  distributed.gather_success (one RCCL all-gather of 64 B per rank) + CurriculumSchedule after every rollout.
 
 The torch policy is the master copy of the weights; after every update they are loaded into the HIP head
-(DeviceActor.load_policy).  Multi-GPU: every rank collects its shard; gradients are averaged with one all-reduce per
+(DeviceActor.load_policy; with update="hip" the parameters are views of the learner's flat device buffer and the head is
+repacked on the device).  Multi-GPU: every rank collects its shard; gradients are averaged with one all-reduce per
 minibatch step when torch.distributed is initialised (data-parallel PPO)."""
 import math
 
@@ -80,13 +83,16 @@ class PPO(object):
     every update (the reference's monitor_training)."""
 
     def __init__(self, vec, policy=None, seed=0, fused=None, graph=True, curriculum=None, group=None, precise=True,
-                 graph_update=True, **kw):
+                 graph_update=True, update="torch", **kw):
         from .actor import DeviceActor
         hp = dict(PPO2_DEFAULTS)
         unknown = set(kw) - set(hp)
         if unknown:
             raise TypeError("unknown PPO hyper-parameters: {}".format(sorted(unknown)))
         hp.update(kw)
+        if update not in ("torch", "hip"):
+            raise ValueError("update must be 'torch' or 'hip', not {!r}".format(update))
+        self.update_path = update
         self.hp, self.vec, self.group = hp, vec, group
         self.n_steps = int(hp["n_steps"])
         self._torch_dev = getattr(vec._mem, "device", torch.device("cpu"))
@@ -98,8 +104,13 @@ class PPO(object):
         self.rollout = FusedRollout(vec, self.actor, self.n_steps, **self._rollout_kw)
         self._spec_at_capture = vec.spec_index
         on_gpu = self._torch_dev.type == "cuda"
-        # (GPU: the fused, capturable form -- ONE launch for all thirteen parameter tensors inside the captured minibatch step)
-        self.opt = torch.optim.Adam(self.policy.parameters(), lr=hp["learning_rate"], eps=1e-5, **({"capturable": True, "fused": True} if on_gpu else {}))
+        if update == "hip":   # (the module's parameters become views of the learner's flat buffer; no torch optimiser)
+            from .learner import HipLearner
+            self.opt, self._lr = None, hp["learning_rate"]
+            self.learner = HipLearner(vec._lib, self.actor, self.policy, self._torch_dev, graph=bool(graph_update) and on_gpu)
+        else:
+            # (GPU: the fused, capturable form -- ONE launch for all thirteen parameter tensors inside the captured minibatch step)
+            self.opt = torch.optim.Adam(self.policy.parameters(), lr=hp["learning_rate"], eps=1e-5, **({"capturable": True, "fused": True} if on_gpu else {}))
         self._graph_update, self._step_graph = bool(graph_update) and on_gpu, None
         self.curriculum = curriculum
         m, N, T = vec._mem, vec.num_envs, self.n_steps
@@ -192,7 +203,22 @@ class PPO(object):
         g["acc"].zero_()
         return g
 
+    def _update_hip(self, batch, lr, cliprange):
+        """The same update on the HIP learner: the same permutations from the same generator calls as the torch path."""
+        hp = self.hp
+        n = batch["obs"].shape[0]
+        nmb = int(hp["nminibatches"])
+        if lr is not None:   # (as the torch path: a given lr stays in force)
+            self._lr = lr
+        perms = [torch.randperm(n, device=self._torch_dev, generator=self._gen) for _ in range(int(hp["noptepochs"]))]
+        stats = self.learner.update(batch, perms, n // nmb, nmb, self._lr, hp["cliprange"] if cliprange is None else cliprange,
+                                    hp["ent_coef"], hp["vf_coef"], hp["max_grad_norm"], world=self._world, group=self.group)
+        self.updates += 1
+        return stats
+
     def update(self, batch, lr=None, cliprange=None):
+        if self.update_path == "hip":
+            return self._update_hip(batch, lr, cliprange)
         hp = self.hp
         n = batch["obs"].shape[0]
         mb = n // int(hp["nminibatches"])

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FWG_ABI_VERSION 20
+#define FWG_ABI_VERSION 21
 
 #define FWG_N_VARS 23        /* simulator variables, see fwg_var */
 #define FWG_N_RESET_VARS 21  /* the keys of reset(state=...) records (fixed_wing.py:287,308; test-set format) */
@@ -475,6 +475,62 @@ int fwg_rollout_step(fwg_handle* env, fwg_actor* head, float* norm_obs_out, floa
  * (1 - done_t) - V_t; ret = adv + V.  One launch on `stream`, no synchronisation, no allocation. */
 int fwg_gae(int64_t n_steps, int64_t n_envs, const float* rewards, const float* values, const uint8_t* dones,
             const float* last_value, float gamma, float lam, float* adv_out, float* ret_out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * PPO update ("learner"): the minibatch step of stable-baselines' PPO2 (ppo2.py setup_model / _train_step) behind
+ * `PPO2(MlpPolicy, env).learn(...)` (examples/train_rl_controller.py:223-232) on the rollout head's 64-64 networks, as HIP
+ * kernels: per-minibatch advantage normalisation (biased std + 1e-8), clipped surrogate, value loss clipped around the old
+ * value with the same range, entropy of the state-independent log-std, then clip_grad_norm_(max_grad_norm) (coefficient
+ * max_norm / (norm + 1e-6), capped at 1) and torch.optim.Adam(eps) in torch's bias-corrected form with the step count on the
+ * device.  The networks' forward and backward passes run on the matrix cores with split-bf16 operands (fwg_actor_act's
+ * precision).  Parameters, Adam moments and gradients are ONE flat float32 layout, MlpPolicy.parameters() order:
+ *     log_std [act_dim] | pi.0.weight [64][obs_dim], pi.0.bias [64], pi.2.weight [64][64], pi.2.bias [64],
+ *     pi.4.weight [act_dim][64], pi.4.bias [act_dim] | vf.0 ... vf.4 (output width 1)
+ * -- fwg_learner_num_params() floats; a gradient buffer holds 4 more: the minibatch sums of the policy loss, the value loss,
+ * 0.5 (logp - old logp)^2 and the clipped-ratio count.  Minibatch rows are gathered by index from the step-major rollout
+ * buffers (fwg_rollout_step / fwg_actor_act outputs and fwg_gae's, flattened to [n_steps * n_envs]).  Every call takes
+ * device pointers and a stream, neither synchronises nor allocates (stream-capturable), and sums in a fixed order: two
+ * runs on the same inputs agree bit for bit.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fwg_learner fwg_learner;
+
+/* Hyper-parameters, read on the DEVICE at every launch (a captured update follows changes without recapture):
+ * learning rate, clip range (policy and value), entropy and value coefficients, max gradient norm, Adam betas and eps --
+ * doubles, as the Python scalars torch's optimiser derives its float factors from. */
+typedef struct fwg_ppo_hparams {
+    double lr, cliprange, ent_coef, vf_coef, max_grad_norm, beta1, beta2, eps;
+} fwg_ppo_hparams;
+
+/* The rollout as the update reads it, rows indexed by the minibatch index arrays: obs [n][obs_dim], actions [n][act_dim],
+ * values / logp (log-probability of the action at sampling time) / adv / returns [n]. */
+typedef struct fwg_ppo_batch {
+    const float *obs, *actions, *values, *logp, *adv, *returns;
+} fwg_ppo_batch;
+
+/* A learner for `head`'s networks (obs_dim, act_dim, device); it owns its partial-gradient scratch (~10 MB) and writes the
+ * head's packed weights in fwg_actor_pack.  Destroy it before the head. */
+int fwg_learner_create(fwg_actor* head, fwg_learner** out);
+void fwg_learner_destroy(fwg_learner* L);
+int64_t fwg_learner_num_params(const fwg_learner* L);
+/* Once per epoch: moments [n_minibatches][2] = mean and std (biased) + 1e-8 of adv over the rows
+ * perm[k mb ... (k + 1) mb) (int64 row indices) of every minibatch k (ppo2.py: advs normalised per minibatch). */
+int fwg_ppo_moments(fwg_learner* L, const float* adv, const int64_t* perm, int64_t mb, int n_minibatches, float* moments, void* stream);
+/* The gradient half: d(pg_loss - ent_coef entropy + vf_coef vf_loss) / d params over the mb rows idx[0 .. mb) with this
+ * minibatch's `moments` [2] -> grad_out [num_params + 4] (unclipped, loss sums appended).  For data-parallel training:
+ * all-reduce grad_out, divide by the world size, then fwg_ppo_apply. */
+int fwg_ppo_grad(fwg_learner* L, const fwg_ppo_batch* b, const int64_t* idx, int64_t mb, const float* moments, const float* params,
+                 const fwg_ppo_hparams* hp, float* grad_out, void* stream);
+/* The apply half: clip_grad_norm_ + Adam on params / adam_m / adam_v (each [num_params]) from `grad` ([num_params + 4]),
+ * *step += 1; stats_acc [5] += pg_loss, vf_loss, entropy, approx_kl, clip_frac of the minibatch (sums / mb; entropy of the
+ * log-std before the step), the order of gym_fixed_wing.ppo.STAT_KEYS. */
+int fwg_ppo_apply(fwg_learner* L, const float* grad, int64_t mb, const fwg_ppo_hparams* hp, float* params, float* adam_m, float* adam_v,
+                  int32_t* step, float* stats_acc, void* stream);
+/* One full minibatch step: fwg_ppo_grad into the learner's own gradient buffer, then fwg_ppo_apply (three launches). */
+int fwg_ppo_step(fwg_learner* L, const fwg_ppo_batch* b, const int64_t* idx, int64_t mb, const float* moments, const fwg_ppo_hparams* hp,
+                 float* params, float* adam_m, float* adam_v, int32_t* step, float* stats_acc, void* stream);
+/* The head's weights from the flat parameters, on the device: what fwg_actor_set_weights does from host arrays, with no host
+ * round trip (a captured rollout sees the new weights at its next replay). */
+int fwg_actor_pack(fwg_learner* L, const float* params, void* stream);
 
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);
