@@ -17,7 +17,12 @@ per rank with global env ids, the only collective is the RCCL all-gather of the 
 
 The timed region replays the K launches from hipGraphs (no per-launch host work), bracketed by barrier + synchronize;
 `value` and `roofline` are both computed from that ONE wall-clock interval (max over ranks).  Prints ONE JSON line on
-rank 0 with `roofline` and (N = 1) `cpu_baseline` objects.
+rank 0 with a `roofline` object.
+
+A plain run does only what that line needs: set-up, the untimed and W warm-up steps, the K timed steps, --dump-outputs,
+the line.  --full adds everything that takes runs of its own, after the timed steps: the side measurements (steady
+state, observation consumers, the other configurations and kernel tiers, the PPO rollout loop and training) and, on one
+GPU, the `cpu_baseline` object.
 """
 import argparse
 import hashlib
@@ -282,9 +287,12 @@ def main():
     ap.add_argument("--workload", default="c3", choices=["c3", "c2", "c4", "c5"])
     ap.add_argument("--envs", type=int, default=0, help="envs per GPU (default: the workload's)")
     ap.add_argument("--total-envs", type=int, default=0, help="fixed TOTAL number of envs sharded over the ranks (strong scaling)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--cpu-procs", type=int, default=0, help="oracle processes of the CPU baseline (default 0 = one per host core)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements and (1 GPU) the CPU baseline and report them in "
+                         "the line (default: the headline figure alone)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: seconds of the CPU baseline's sample")
+    ap.add_argument("--cpu-procs", type=int, default=0, help="with --full: oracle processes of the CPU baseline (default 0 = one per host core)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--obs-layout", default="auto", choices=["auto", "dense", "log"],
                     help="'auto' (default) = the env's default: lagged matrix observations are kept once as a row log and "
                          "handed out as a zero-copy window / read in place by the rollout head; 'dense' = fwg_step writes "
@@ -305,10 +313,10 @@ def main():
                     help="S > 0: before the warm-up, reset 1/S of the envs every steps_max/S steps, so that episode ends (metrics, "
                          "success reduction, in-kernel auto-reset, early-episode observation padding) are spread evenly over the "
                          "timed steps -- the steady state of a long run.  Default 0: all envs start together as a fresh VecEnv "
-                         "does (no episode ends inside a short timed region); the steady state is then measured as well and "
-                         "reported as `steady_state` next to `value` (1 GPU, env-step workloads)")
+                         "does (no episode ends inside a short timed region); with --full the steady state is then measured as well "
+                         "and reported as `steady_state` next to `value` (1 GPU, env-step workloads)")
     ap.add_argument("--no-side", "--no-steady-state", dest="no_side", action="store_true",
-                    help="skip the side measurements (steady state, observation consumer, dense layout, c2, integrator 4x64)")
+                    help="with --full: skip the side measurements (steady state, observation consumer, dense layout, c2, integrator 4x64)")
     ap.add_argument("--emulate", action="store_true",
                     help="TEST ONLY: host-emulation build of the kernels + gloo, tiny batch (exercises the launcher, the "
                          "sharding and the collective on a machine without GPUs; the numbers are not measurements)")
@@ -596,9 +604,9 @@ def main():
         dumped = dump_outputs(args.dump_outputs, last_step_outputs(vec, get_rollout(chunk) if fused and chunk else None), first,
                               DUMP_BYTES // world, "_rank{}".format(rank) if world > 1 else "")
 
-    # ---- side measurements (same launches, other regimes / consumers / configurations); never part of `value`
+    # ---- side measurements (same launches, other regimes / consumers / configurations); never part of `value`, --full only
     sides = {}
-    side_ok = graphs and not fused and not args.emulate and not args.no_side
+    side_ok = args.full and graphs and not fused and not args.emulate and not args.no_side
     if side_ok and replays and chunk != SIDE_CHUNK:
         # What the timed region is made of: T(c) = c x k + F per replayed chunk (k: one step kernel in a replayed graph; F: the
         # chunk's fixed cost -- graph launch from an idle device, episode collection + success sums, host launch + wake-up).
@@ -903,7 +911,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and not args.emulate:   # after the process group is gone
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.emulate:   # after the process group is gone
             out["cpu_baseline"] = cpu_baseline("c3" if args.workload == "c4" else args.workload, args.cpu_seconds, args.cpu_procs)
         sys.stdout.flush()
         try:   # RCCL's banner sits in the C stdio buffer until exit when stdout is a pipe: push it out first

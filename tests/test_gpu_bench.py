@@ -20,7 +20,7 @@ def _last_json(out):
 
 
 def test_bench_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "300", "--warmup", "50",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "300", "--warmup", "50",
                           "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _last_json(out.stdout)
@@ -41,11 +41,11 @@ def test_bench_through_torchrun_with_rccl():
 
 
 def test_bench_line_carries_the_rollout_and_training_figures():
-    """BASELINE configs[4] (the PPO rollout loop) rides in the default line: `c5` = the library's default two-launch path, `c5_fused`
+    """BASELINE configs[4] (the PPO rollout loop) rides in the --full line: `c5` = the library's default two-launch path, `c5_fused`
     (+ `c5_fused_bf16`) = the opt-in one-launch step, `c5_train` = with advantages and the optimiser; `timed_region` splits the
     driver's line into kernel time per step and fixed cost per chunk."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
-                         capture_output=True, text=True, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5",
+                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _last_json(out.stdout)
     for k in ("c5", "c5_fused", "c5_fused_bf16", "c5_train", "steady_state", "obs_delivered", "c2", "timed_region"):
@@ -57,6 +57,17 @@ def test_bench_line_carries_the_rollout_and_training_figures():
     assert 5.0 < tr["kernel_us_per_step"] < 20.0 and 0.0 < tr["fixed_us_per_chunk"] < 200.0
     # the zero-copy window costs what the step costs (a gathered copy would be 1.5x)
     assert j["obs_delivered"]["route"] == "row_log_view" and j["obs_delivered"]["ms_per_step"] < 1.15 * j["steady_state"]["ms_per_step"]
+
+
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full the line holds the headline figure of the timed steps and nothing that takes runs of its own: no side
+    measurement, no CPU baseline."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "300", "--warmup", "50"],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = _last_json(out.stdout)
+    assert KEYS - {"cpu_baseline"} <= set(j) and j["steps"] == 300 and j["warmup"] == 50 and j["value"] > 1e9
+    assert not {"cpu_baseline", "timed_region", "steady_state", "obs_delivered", "c2", "c5", "c5_train"} & set(j), sorted(j)
 
 
 def test_two_rank_rccl_smoke():
