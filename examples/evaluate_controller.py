@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Evaluation protocol of the reference (examples/evaluate_controller.py:44-169 there) on the MI355X env: flies a test
 set of (initial state, target) scenarios, all scenarios in one batch, with the PID baseline or a stable-baselines MLP
-policy (through the HIP rollout head), and prints the table of examples/README.md:33-47.
+policy or the CnnMlpPolicy of the shipped CNN controller (both through the HIP rollout head), and prints the table of
+examples/README.md:33-47.  For the CNN controller the first action of every episode is computed from the un-normalised reset
+observation, as the reference's script does (evaluate_controller.py:118 there; the protocol its published CNN row carries).
 
     python examples/evaluate_controller.py --controller pid
     python examples/evaluate_controller.py --controller mlp --model tests/golden/mlp_controller.json
+    python examples/evaluate_controller.py --controller cnn     (model: tests/golden/cnn_controller.npz)
 
 Test-set format: JSON list of {"state": {...}, "target": {...}} (converted from the reference's .npy test sets; the one
 under tests/golden/ is its examples/test_sets/test_set_wind_none_step20-20-3.npy)."""
@@ -21,10 +24,11 @@ from gym_fixed_wing import evaluate as ev, presets  # noqa: E402
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--controller", default="pid", choices=["pid", "mlp"])
+    ap.add_argument("--controller", default="pid", choices=["pid", "mlp", "cnn"])
     ap.add_argument("--test-set", default=os.path.join(ROOT, "tests", "golden", "test_set_wind_none.json"))
-    ap.add_argument("--model", default=os.path.join(ROOT, "tests", "golden", "mlp_controller.json"),
-                    help="JSON with 'weights' (stable-baselines MlpPolicy parameters) and 'obs_rms' {mean, var}")
+    ap.add_argument("--model", default=None,
+                    help="converted checkpoint (actor.load_controller): stable-baselines MlpPolicy / CnnMlpPolicy weights and obs_rms; "
+                         "default tests/golden/mlp_controller.json / cnn_controller.npz")
     ap.add_argument("--turbulence", default="none", choices=["none", "light", "moderate", "severe"])
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
@@ -33,14 +37,22 @@ def main():
     if args.controller == "pid":
         res = ev.evaluate_on_set(scenarios, presets.preset("examples"), turbulence_intensity=args.turbulence, device=args.device)
     else:
-        from gym_fixed_wing.actor import DeviceActor, weights_from_stable_baselines
-        with open(args.model) as f:
-            m = json.load(f)
-        actor = DeviceActor(len(scenarios), len(m["obs_rms"]["mean"]), training=False, device=args.device)
-        actor.load_policy(weights_from_stable_baselines(m["weights"]))
-        actor.set_stats(m["obs_rms"]["mean"], m["obs_rms"]["var"], 1e6)
-        res = ev.evaluate_on_set(scenarios, presets.preset("mlp"), turbulence_intensity=args.turbulence, device=args.device,
-                                 policy=lambda obs: actor.act(obs.reshape(obs.shape[0], -1).contiguous(), deterministic=True)[1])
+        import numpy as np
+        from gym_fixed_wing.actor import DeviceActor, load_controller, module_from_weights, weights_from_stable_baselines
+        model = args.model or os.path.join(ROOT, "tests", "golden", "mlp_controller.json" if args.controller == "mlp" else "cnn_controller.npz")
+        m = load_controller(model)
+        w = weights_from_stable_baselines(m["weights"])
+        obs_dim = int(np.asarray(m["obs_rms"]["mean"]).size)
+        actor = DeviceActor(len(scenarios), obs_dim, training=False, device=args.device)
+        actor.load_policy(w)
+        actor.set_stats(np.asarray(m["obs_rms"]["mean"]).reshape(-1), np.asarray(m["obs_rms"]["var"]).reshape(-1), 1e6)
+        first = None
+        if "c1_w" in w:   # the first action of an episode: the same network on the raw observation (torch fp32)
+            net = module_from_weights(w, np.asarray(m["obs_rms"]["mean"]).shape).to("cuda:{}".format(args.device))
+            first = lambda obs: net.pi(obs.reshape(obs.shape[0], -1))
+        res = ev.evaluate_on_set(scenarios, presets.preset(args.controller), turbulence_intensity=args.turbulence, device=args.device,
+                                 policy=lambda obs: actor.act(obs.reshape(obs.shape[0], -1).contiguous(), deterministic=True)[1],
+                                 first_step_policy=first)
     t = ev.summarize(res)
     print("controller {}, {} scenarios, turbulence {}".format(args.controller, len(scenarios), args.turbulence))
     print("success %      roll {roll:6.1f}  pitch {pitch:6.1f}  Va {Va:6.1f}  all {all:6.1f}".format(**t["success_%"]))

@@ -5,6 +5,7 @@ its callback, :80-87) with the whole data path on the device: rollouts by the HI
 the PPO2 update in torch on the same buffers (or, with --update hip, as HIP kernels: gym_fixed_wing/learner.py), the success sums all-gathered over RCCL, the curriculum raised on every rank.
 
     python examples/train_ppo.py --envs 4096 --timesteps 100e6 --out model.npz
+    python examples/train_ppo.py --policy cnn --envs 4096 --timesteps 100e6 --out cnn_model.npz   (the CNN controller)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_ppo.py --envs 32768
 
 The reference trains 4 sub-process envs for 5 M steps (~8 h of PyFly on 4 cores; examples/tensorboard.png: success_all ~0.8 at
@@ -26,17 +27,26 @@ import torch.distributed as dist  # noqa: E402
 
 from gym_fixed_wing import presets  # noqa: E402
 from gym_fixed_wing.distributed import CurriculumSchedule, make_sharded_env  # noqa: E402
-from gym_fixed_wing.ppo import PPO  # noqa: E402
+from gym_fixed_wing.ppo import PPO, sb_init_  # noqa: E402
+from gym_fixed_wing.rollout import CnnMlpPolicy  # noqa: E402
 
 
 def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, learning_rate=5e-4, n_steps=128, curriculum=True,
-          config="examples", log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch"):
-    vec = make_sharded_env(presets.preset(config), total_envs=envs, rank=rank, world_size=world, device=local, derived_views=False,
-                           seed=seed)
+          config=None, log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch", policy="mlp"):
+    """policy: "mlp" (MlpPolicy on the examples config's 12-vector) or "cnn" (CnnMlpPolicy on the cnn config's 5 x 12 matrix
+    observations: the reference's --policy CNN, train_rl_controller.py:179-197).  config: preset name, default by policy."""
+    config = config or ("cnn" if policy == "cnn" else "examples")
+    # (the cnn configuration's build-time kernel instance is the shipped one, derived views on: presets.SPECIALISED ship_cnn_log)
+    vec = make_sharded_env(presets.preset(config), total_envs=envs, rank=rank, world_size=world, device=local,
+                           derived_views=config == "cnn", seed=seed)
     sched = CurriculumSchedule(level=0.25 if curriculum else 1.0)     # (train_rl_controller.py:162: curriculum_level = 0.25)
     vec.set_curriculum_level(sched.level)
     vec.reset()
-    ppo = PPO(vec, seed=seed, curriculum=sched, n_steps=n_steps, nminibatches=nminibatches, noptepochs=noptepochs,
+    net = None
+    if policy == "cnn":
+        torch.manual_seed(seed)
+        net = sb_init_(CnnMlpPolicy(obs_shape=vec.obs_shape, n_filters=3))
+    ppo = PPO(vec, policy=net, seed=seed, curriculum=sched, n_steps=n_steps, nminibatches=nminibatches, noptepochs=noptepochs,
               learning_rate=learning_rate, fused=fused, ent_coef=ent_coef, update=update)
     t0 = time.perf_counter()
     window = []    # success over the last finished episodes (the reference's ep_info_buf holds the last 100)
@@ -69,6 +79,8 @@ def main():
     ap.add_argument("--ent-coef", type=float, default=0.01)
     ap.add_argument("--disable-curriculum", action="store_true")
     ap.add_argument("--update", choices=("torch", "hip"), default="torch", help="PPO update: torch autograd (default) or the HIP kernels")
+    ap.add_argument("--policy", choices=("mlp", "cnn"), default="mlp",
+                    help="mlp: MlpPolicy, examples config; cnn: CnnMlpPolicy (3 filters), cnn config (torch update only)")
     ap.add_argument("--out", default=None, help="save weights + VecNormalize statistics (.npz)")
     ap.add_argument("--curve", default=None, help="write the learning curve (JSON)")
     args = ap.parse_args()
@@ -78,7 +90,7 @@ def main():
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
     torch.cuda.set_device(local)
     ppo, res = train(args.envs, args.timesteps, args.seed, args.nminibatches, args.noptepochs, args.lr, curriculum=not args.disable_curriculum,
-                     rank=rank, world=world, local=local, ent_coef=args.ent_coef, update=args.update)
+                     rank=rank, world=world, local=local, ent_coef=args.ent_coef, update=args.update, policy=args.policy)
     if rank == 0:
         print("{:.3e} env-steps in {:.1f} s = {:.3e} env-steps/s INCLUDING the optimiser ({} updates)".format(
             ppo.num_timesteps, res["seconds"], res["env_steps_per_s"], res["updates"]))

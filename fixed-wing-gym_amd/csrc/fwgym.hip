@@ -2476,6 +2476,8 @@ struct fwg_actor {
     float* d_log_std;
     float* d_ret;
     size_t lds_act[2];     // dynamic LDS of k_actor_act<1>, <3>
+    int cnn_filters, cnn_rows;   // fwg_actor_set_conv: CNN front end (k_actor_act_cnn); 0 = the MLP on the flattened observation
+    size_t lds_cnn[2];     // dynamic LDS of k_actor_act_cnn<1>, <3>
     const fwg_handle* log_env;   // fwg_actor_set_obs_log: `obs` arguments are this env's row log
 #ifdef FWG_TIMELINE
     long long* trace;
@@ -2541,6 +2543,8 @@ int fwg_actor_set_obs_log(fwg_actor* a, const fwg_handle* env) {
         if (env->h.obs_log <= 0) return fail_with(FWG_ERR_INVALID, "fwg_actor_set_obs_log: the env writes the dense observation batch");
         if (env->n_envs != a->n_envs || env->h.obs_dim != a->D || env->device != a->device || (env->h.n_obs & 3))
             return fail_with(FWG_ERR_INVALID, "fwg_actor_set_obs_log: batch size / observation size / device mismatch (n_obs must be a multiple of 4)");
+        if (a->cnn_filters && env->h.n_obs * a->cnn_rows != a->D)
+            return fail_with(FWG_ERR_INVALID, "fwg_actor_set_obs_log: the CNN head's conv spans a window of another length than the env's");
     }
     a->log_env = env;
     return FWG_OK;
@@ -2565,8 +2569,8 @@ int fwg_actor_create(int device, int64_t n_envs, int obs_dim, int act_dim, float
     HIP_TRY(hipMalloc((void**)&a->d_acc, acc_bytes));
     HIP_TRY(hipMemset(a->d_acc, 0, acc_bytes));
     HIP_TRY(hipMalloc((void**)&a->d_frags, nfrag * sizeof(frag_t)));
-    HIP_TRY(hipMalloc((void**)&a->d_bias, 2 * FWG_ACT_BIAS_FLOATS * sizeof(float)));
-    HIP_TRY(hipMemset(a->d_bias, 0, 2 * FWG_ACT_BIAS_FLOATS * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&a->d_bias, (2 * FWG_ACT_BIAS_FLOATS + FWG_CNN_PARAMS) * sizeof(float)));   // (+ the conv, behind)
+    HIP_TRY(hipMemset(a->d_bias, 0, (2 * FWG_ACT_BIAS_FLOATS + FWG_CNN_PARAMS) * sizeof(float)));
     HIP_TRY(hipMalloc((void**)&a->d_log_std, FWG_ACT_MAX_ACT * sizeof(float)));
     HIP_TRY(hipMalloc((void**)&a->d_ret, (size_t)n_envs * sizeof(float)));
     HIP_TRY(hipMemset(a->d_frags, 0, nfrag * sizeof(frag_t)));
@@ -2612,7 +2616,8 @@ int fwg_actor_set_weights(fwg_actor* a, const fwg_actor_weights* w) {
         const float* w1 = net ? w->vf_w1 : w->pi_w1; const float* b1 = net ? w->vf_b1 : w->pi_b1;
         const float* w2 = net ? w->vf_w2 : w->pi_w2; const float* b2 = net ? w->vf_b2 : w->pi_b2;
         const int out = net ? 1 : a->act_dim;
-        actor_pack_layer(hi, lo, w0, 64, a->D, 2, a->nk1, false, FWG_ACT_PRESCALE);
+        const int in0 = a->cnn_filters ? a->cnn_filters * (a->D / a->cnn_rows) : a->D;   // (CNN: layer 0 takes the conv outputs)
+        actor_pack_layer(hi, lo, w0, 64, in0, 2, a->nk1, false, FWG_ACT_PRESCALE);
         actor_pack_layer(hi, lo, w1, 64, 64, 2, 4, true, FWG_ACT_PRESCALE);
         actor_pack_layer(hi, lo, w2, out, 64, 1, 4, true, 1.f);
         all.insert(all.end(), hi.begin(), hi.end());
@@ -2626,6 +2631,38 @@ int fwg_actor_set_weights(fwg_actor* a, const fwg_actor_weights* w) {
     float ls[FWG_ACT_MAX_ACT] = {0.f, 0.f, 0.f, 0.f};
     for (int i = 0; i < a->act_dim; ++i) ls[i] = w->log_std[i];
     HIP_TRY(hipMemcpy(a->d_log_std, ls, sizeof(ls), hipMemcpyHostToDevice));
+    return FWG_OK;
+}
+
+int fwg_actor_set_conv(fwg_actor* a, int n_filters, int rows, const float* w, const float* b) {
+    if (!a) return fail_with(FWG_ERR_INVALID, "fwg_actor_set_conv: null handle");
+    if (n_filters == 0) {   // back to the MLP on the flattened observation
+        a->cnn_filters = a->cnn_rows = 0;
+        a->nk1 = (a->D + 15) / 16;
+        return FWG_OK;
+    }
+    if (!w || !b) return fail_with(FWG_ERR_INVALID, "fwg_actor_set_conv: null weight array");
+    if (rows < 2 || a->D % rows != 0)
+        return fail_with(FWG_ERR_INVALID, "fwg_actor_set_conv: needs matrix observations (obs_dim = rows x features, rows >= 2)");
+    const int features = a->D / rows;
+    if (a->log_env != nullptr && a->log_env->h.n_obs != features)
+        return fail_with(FWG_ERR_INVALID, "fwg_actor_set_conv: rows must be the observation length -- the conv spans the whole window (output height 1)");
+    if (n_filters < 1 || n_filters * features > 64)
+        return fail_with(FWG_ERR_INVALID, "fwg_actor_set_conv: n_filters x features must be in [1, 64] (layer 0 of the 64-64 networks)");
+    if (rows != FWG_CNN_ROWS || features != FWG_CNN_COLS || n_filters != FWG_CNN_FILTERS)
+        return fail_with(FWG_ERR_INVALID, "fwg_actor_set_conv: this build's CNN head is the shipped controller's 5 x 12 window with 3 filters");
+    HIP_TRY(hipSetDevice(a->device));
+    float p[FWG_CNN_PARAMS];
+    memset(p, 0, sizeof(p));
+    for (int i = 0; i < rows * n_filters; ++i) p[i] = w[i];
+    for (int c = 0; c < n_filters; ++c) p[rows * n_filters + c] = b[c];
+    HIP_TRY(hipMemcpy(a->d_bias + 2 * FWG_ACT_BIAS_FLOATS, p, sizeof(p), hipMemcpyHostToDevice));
+    a->lds_cnn[0] = actor_lds_bytes(FWG_CNN_NK1, 1);
+    a->lds_cnn[1] = actor_lds_bytes(FWG_CNN_NK1, 2);
+    HIP_TRY(hipFuncSetAttribute((const void*)k_actor_act_cnn<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->lds_cnn[0]));
+    HIP_TRY(hipFuncSetAttribute((const void*)k_actor_act_cnn<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->lds_cnn[1]));
+    a->cnn_filters = n_filters; a->cnn_rows = rows;
+    a->nk1 = FWG_CNN_NK1;
     return FWG_OK;
 }
 
@@ -2690,6 +2727,13 @@ int fwg_actor_act(fwg_actor* a, const float* obs, const float* reward, const uin
     A.done_out = done_out; A.deterministic = deterministic ? 1 : 0;
     const dim3 grid((unsigned)((a->n_envs + FWG_ACT_ENVS - 1) / FWG_ACT_ENVS)), block(64 * FWG_ACT_WAVES);
     hipStream_t st = (hipStream_t)stream;
+    if (a->cnn_filters) {
+        if (a->precise) hipLaunchKernelGGL((k_actor_act_cnn<3>), grid, block, a->lds_cnn[1], st, A);
+        else hipLaunchKernelGGL((k_actor_act_cnn<1>), grid, block, a->lds_cnn[0], st, A);
+        HIP_TRY(hipGetLastError());
+        a->parity ^= 1;
+        return FWG_OK;
+    }
 #define FWG_ACT_LAUNCH(NK)                                                                                \
     case NK:                                                                                              \
         if (a->precise) hipLaunchKernelGGL((k_actor_act<3, NK>), grid, block, a->lds_act[1], st, A);     \
@@ -2746,7 +2790,7 @@ extern "C" {
 int fwg_rollout_available(const fwg_handle* h, const fwg_actor* a) {
     if (!h || !a || h->observer != a || h->spec < 0 || !h->split || h->h.obs_log > 0) return 0;
     if (h->h.model_n > 0 || h->h.randomize_scaling) return 0;   // (the per-env parameter queue launch sits between head and step)
-    if (a->act_dim != 3 || a->log_env != nullptr) return 0;
+    if (a->act_dim != 3 || a->log_env != nullptr || a->cnn_filters) return 0;   // (k_rollout runs the MLP head only)
     if (!h->rollout_lds_granted) return 0;
     return launch_rollout(const_cast<fwg_handle*>(h), const_cast<fwg_actor*>(a), KArgs(), ActorArgs(), nullptr, true) == 0 ? 1 : 0;
 }
@@ -2826,6 +2870,7 @@ extern "C" {
 
 int fwg_learner_create(fwg_actor* head, fwg_learner** out) {
     if (!head || !out) return fail_with(FWG_ERR_INVALID, "fwg_learner_create: null argument");
+    if (head->cnn_filters) return fail_with(FWG_ERR_INVALID, "fwg_learner_create: the HIP PPO update has no backward pass through the conv of a CNN head");
     HIP_TRY(hipSetDevice(head->device));
     fwg_learner* L = new fwg_learner();
     L->head = head;

@@ -62,6 +62,34 @@ struct ActorArgs {
 // frags per network and part: layer 1: 2 row tiles x nk1, layer 2: 2 x 4, layer 3: 1 x 4 (the biases are kept apart, in fp32)
 __host__ __device__ inline int actor_frags(int nk1) { return 2 * nk1 + 2 * 4 + 4; }
 #define FWG_ACT_BIAS_FLOATS 160   /* per network: layer 1 (64) | layer 2 (64) | layer 3 (32, act_dim / 1 used) */
+
+// CNN front end (include/fwgym.h fwg_actor_set_conv): the CnnMlpPolicy of the reference's shipped CNN controller
+// (examples/train_rl_controller.py:179-197 --policy CNN, examples/models/cnn_controller: policy_kwargs n_filters 3, Box(5, 12)).
+// One VALID conv whose kernel spans the whole 5-row window (output height 1), 1 column wide, shared by all 12 features and by pi
+// and vf: y[j][c] = act(b[c] + sum_r w[r][c] x[r][j]); the 36 values are layer 0's input (K = 36: three k-blocks instead of the
+// flattened window's four).  The two readings the checkpoint leaves open were settled on the float64 oracle against the
+// published closed-loop rewards of that controller (tools/cnn_trace.py, profiles/cnn_architecture.txt):
+#define FWG_CNN_ROWS 5
+#define FWG_CNN_COLS 12
+#define FWG_CNN_FILTERS 3
+#define FWG_CNN_K (FWG_CNN_COLS * FWG_CNN_FILTERS)
+#define FWG_CNN_NK1 ((FWG_CNN_K + 15) / 16)
+#define FWG_CNN_ACT_IDENTITY 0
+#define FWG_CNN_ACT_TANH 1
+#define FWG_CNN_ACT_RELU 2
+#define FWG_CNN_ACTIVATION FWG_CNN_ACT_TANH   /* A: tanh after the conv */
+#define FWG_CNN_FEATURE_MAJOR 1               /* F: input k = j * FILTERS + c (TF's NHWC reshape, SB2 conv_to_fc) */
+// the conv parameters ride behind the two networks' biases: bias[2 FWG_ACT_BIAS_FLOATS + r FILTERS + c] = w[r][c], then b[c]
+#define FWG_CNN_PARAMS 32
+
+// conv input k of the 36 -> (feature j, filter c)
+__host__ __device__ constexpr int cnn_feature(int k) { return FWG_CNN_FEATURE_MAJOR ? k / FWG_CNN_FILTERS : k % FWG_CNN_COLS; }
+__host__ __device__ constexpr int cnn_filter(int k) { return FWG_CNN_FEATURE_MAJOR ? k % FWG_CNN_FILTERS : k / FWG_CNN_COLS; }
+__device__ __forceinline__ float cnn_activation(float z) {
+    if (FWG_CNN_ACTIVATION == FWG_CNN_ACT_TANH) return tanhf(z);
+    if (FWG_CNN_ACTIVATION == FWG_CNN_ACT_RELU) return fmaxf(z, 0.f);
+    return z;
+}
 // logical input index of k-slot (kk, half, t): first layer = features in order; later layers = the accumulator
 // registers of the previous layer in register order (see the header comment)
 __host__ __device__ inline int k_input(int kk, int half, int t) { return 16 * kk + 8 * half + t; }
@@ -376,7 +404,10 @@ struct ActorLds {
 __host__ __device__ inline int actor_weight_floats(int nk1, int parts) { return 2 * parts * actor_frags(nk1) * 64 * 4; }
 __host__ __device__ inline int actor_scratch_floats() { return 2 * FWG_ACT_MAX_OBS + 4 + 2 * FWG_ACT_MAX_OBS + 4 + 2 * FWG_ACT_BIAS_FLOATS; }
 
-template <int SPLIT, int NK1>
+// CNN (k_actor_act_cnn): every lane reads its environment's whole 5 x 12 window (the lanes j and j + 32 of a tile share the
+// environment), normalises it, runs the conv for all 36 outputs on the VALU (180 FMAs, next to the 72 MFMAs of the networks) and
+// keeps the 24 its k-slots of layer 0 need; each half of the tile writes half of the normalised observation
+template <int SPLIT, int NK1, bool CNN = false>
 __device__ __forceinline__ unsigned actor_block(const ActorArgs& A, const ActorLds& Z, long env_first) {
     const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6, j = l & 31, half = l >> 5;
     constexpr int nf = 2 * NK1 + 12;
@@ -411,9 +442,18 @@ __device__ __forceinline__ unsigned actor_block(const ActorArgs& A, const ActorL
     const bool valid = e < A.N;
     const bool vec4 = (A.D & 3) == 0 && (A.obs_n & 3) == 0;
     const long long win = actor_obs_win(A);
-    float raw_x[NK1][8];
+    constexpr int NRAW = CNN ? FWG_CNN_ROWS * FWG_CNN_COLS / 4 : 1;
+    float4 raw_w[NRAW];   // (CNN) the whole window, 4 features per entry
+    float cnn_p[CNN ? FWG_CNN_PARAMS : 1];
+    if constexpr (CNN) {
 #pragma unroll
-    for (int kk = 0; kk < NK1; ++kk) {
+        for (int q = 0; q < NRAW; ++q) raw_w[q] = valid ? *reinterpret_cast<const float4*>(actor_obs_at(A, win, e, 4 * q)) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int i = 0; i < FWG_CNN_PARAMS; ++i) cnn_p[i] = A.bias[2 * FWG_ACT_BIAS_FLOATS + i];   // (uniform: scalar loads)
+    }
+    float raw_x[CNN ? 1 : NK1][8];
+#pragma unroll
+    for (int kk = 0; kk < (CNN ? 0 : NK1); ++kk) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int f0 = k_input(kk, half, 4 * q);
@@ -507,8 +547,40 @@ __device__ __forceinline__ unsigned actor_block(const ActorArgs& A, const ActorL
     FWG_ATL(A, 2);
 
     frag_t bx_hi[NK1], bx_lo[NK1];
+    if constexpr (CNN) {
+        static_assert(NK1 == FWG_CNN_NK1, "CNN head: layer 0 takes the 36 conv outputs");
+        float xn[FWG_CNN_ROWS * FWG_CNN_COLS];
 #pragma unroll
-    for (int kk = 0; kk < NK1; ++kk) {
+        for (int q = 0; q < NRAW; ++q) {
+            const float r4[4] = {raw_w[q].x, raw_w[q].y, raw_w[q].z, raw_w[q].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xn[4 * q + i] = fminf(fmaxf((r4[i] - mean_s[4 * q + i]) * rstd_s[4 * q + i], -A.clip_obs), A.clip_obs);
+            if (A.norm_obs != nullptr && valid && (q < NRAW / 2) == (half == 0))
+                *reinterpret_cast<float4*>(A.norm_obs + e * A.D + 4 * q) = make_float4(xn[4 * q], xn[4 * q + 1], xn[4 * q + 2], xn[4 * q + 3]);
+        }
+        float y[FWG_CNN_K];
+#pragma unroll
+        for (int k = 0; k < FWG_CNN_K; ++k) {
+            const int j = cnn_feature(k), c = cnn_filter(k);
+            float z = cnn_p[FWG_CNN_ROWS * FWG_CNN_FILTERS + c];
+#pragma unroll
+            for (int r = 0; r < FWG_CNN_ROWS; ++r) z = fmaf(cnn_p[r * FWG_CNN_FILTERS + c], xn[r * FWG_CNN_COLS + j], z);
+            y[k] = cnn_activation(z);
+        }
+#pragma unroll
+        for (int kk = 0; kk < NK1; ++kk) {
+            float x[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const int k0 = k_input(kk, 0, t), k1 = k_input(kk, 1, t);
+                const float y0 = k0 < FWG_CNN_K ? y[k0 < FWG_CNN_K ? k0 : 0] : 0.f, y1 = k1 < FWG_CNN_K ? y[k1 < FWG_CNN_K ? k1 : 0] : 0.f;
+                x[t] = half ? y1 : y0;
+            }
+            split8(x, bx_hi[kk], bx_lo[kk]);
+        }
+    }
+#pragma unroll
+    for (int kk = 0; kk < (CNN ? 0 : NK1); ++kk) {
         float x[8];
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -602,6 +674,21 @@ __global__ __launch_bounds__(64 * FWG_ACT_WAVES) void k_actor_act(const ActorArg
     Z.act_out = nullptr;
     Z.bias = Z.misc + 4 + 2 * FWG_ACT_MAX_OBS + 4;
     actor_block<SPLIT, NK1>(A, Z, (long)blockIdx.x * FWG_ACT_ENVS);
+}
+
+// the CNN head (fwg_actor_set_conv): the same LDS layout with layer 0 over the 36 conv outputs
+template <int SPLIT>
+__global__ __launch_bounds__(64 * FWG_ACT_WAVES) void k_actor_act_cnn(const ActorArgs A) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int PARTS = SPLIT > 1 ? 2 : 1;
+    ActorLds Z;
+    Z.F = reinterpret_cast<frag_t*>(lds);
+    Z.mean_s = lds + actor_weight_floats(FWG_CNN_NK1, PARTS);
+    Z.rstd_s = Z.mean_s + FWG_ACT_MAX_OBS;
+    Z.misc = Z.rstd_s + FWG_ACT_MAX_OBS;
+    Z.act_out = nullptr;
+    Z.bias = Z.misc + 4 + 2 * FWG_ACT_MAX_OBS + 4;
+    actor_block<SPLIT, FWG_CNN_NK1, true>(A, Z, (long)blockIdx.x * FWG_ACT_ENVS);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

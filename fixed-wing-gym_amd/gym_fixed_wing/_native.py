@@ -3,7 +3,7 @@ module without a built library raises, there is no CPU fallback."""
 import ctypes as C
 import os
 
-FWG_ABI_VERSION = 21
+FWG_ABI_VERSION = 22
 N_VARS = 23
 N_RESET_VARS = 21
 N_PARAMS = 49
@@ -170,7 +170,7 @@ EXPORTS = ["fwg_abi_version", "fwg_get_layout", "fwg_create", "fwg_destroy", "fw
            "fwg_actor_act", "fwg_attach_observer", "fwg_obs_log_floats", "fwg_obs_window", "fwg_reduce_success_device",
            "fwg_obs_gather", "fwg_actor_set_obs_log", "fwg_selftest_philox", "fwg_rollout_available", "fwg_rollout_step", "fwg_gae",
            "fwg_learner_create", "fwg_learner_destroy", "fwg_learner_num_params", "fwg_ppo_moments", "fwg_ppo_grad", "fwg_ppo_apply",
-           "fwg_ppo_step", "fwg_actor_pack"]
+           "fwg_ppo_step", "fwg_actor_pack", "fwg_actor_set_conv"]
 _libs = {}
 
 
@@ -235,6 +235,7 @@ def load_library(path=None):
     lib.fwg_actor_destroy.argtypes = [vp]
     lib.fwg_actor_destroy.restype = None
     lib.fwg_actor_set_weights.argtypes = [vp, C.POINTER(ActorWeights)]
+    lib.fwg_actor_set_conv.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     lib.fwg_actor_set_stats.argtypes = [vp, C.POINTER(ActorStats), vp]
     lib.fwg_actor_get_stats.argtypes = [vp, C.POINTER(ActorStats), vp]
     lib.fwg_actor_configure.argtypes = [vp, C.c_int, C.c_int]
@@ -272,7 +273,7 @@ def load_library(path=None):
     lib.fwg_actor_pack.argtypes = [vp, vp, vp]
     for name in ("fwg_ppo_moments", "fwg_ppo_grad", "fwg_ppo_apply", "fwg_ppo_step", "fwg_actor_pack"):
         getattr(lib, name).restype = C.c_int
-    for name in ("fwg_actor_create", "fwg_actor_set_weights", "fwg_actor_set_stats", "fwg_actor_get_stats",
+    for name in ("fwg_actor_create", "fwg_actor_set_weights", "fwg_actor_set_conv", "fwg_actor_set_stats", "fwg_actor_get_stats",
                  "fwg_actor_configure", "fwg_actor_seed", "fwg_actor_observe", "fwg_actor_act"):
         getattr(lib, name).restype = C.c_int
     for name in ("fwg_get_layout", "fwg_create", "fwg_destroy", "fwg_update_config", "fwg_seed", "fwg_reset",

@@ -9,6 +9,7 @@ cores + sample).  No CPU path: without the HIP library the constructor raises.""
 import ctypes
 
 import numpy as np
+from torch import nn
 
 from . import _native as nat
 
@@ -16,11 +17,16 @@ _KEYS = ["pi_w0", "pi_b0", "pi_w1", "pi_b1", "pi_w2", "pi_b2", "vf_w0", "vf_b0",
 
 
 def weights_from_module(policy):
-    """torch MlpPolicy of gym_fixed_wing.rollout (pi / vf nn.Sequential + log_std) -> dict of float32 arrays."""
+    """torch MlpPolicy / CnnMlpPolicy of gym_fixed_wing.rollout (pi / vf nn.Sequential + log_std) -> dict of float32 arrays;
+    a CnnMlpPolicy adds its conv as c1_w [rows][n_filters], c1_b [n_filters]."""
     out = {}
+    conv = getattr(policy, "conv", None)
+    if conv is not None:
+        out["c1_w"] = conv.weight.detach().cpu().numpy().astype(np.float32)
+        out["c1_b"] = conv.bias.detach().cpu().numpy().astype(np.float32)
     for net in ("pi", "vf"):
         seq = getattr(policy, net)
-        lin = [m for m in seq if hasattr(m, "weight")]
+        lin = [m for m in seq if isinstance(m, nn.Linear)]
         assert len(lin) == 3, "MlpPolicy layout: three Linear layers per network"
         for i, m in enumerate(lin):
             out["{}_w{}".format(net, i)] = m.weight.detach().cpu().numpy().astype(np.float32)
@@ -31,8 +37,11 @@ def weights_from_module(policy):
 
 def weights_from_stable_baselines(params):
     """Parameter dict of a stable-baselines (TF1) MlpPolicy checkpoint -- kernels are [in][out] there (the layout of the
-    shipped examples/models/mlp_controller, tests/golden/mlp_controller.json) -> torch layout [out][in]."""
+    shipped examples/models/mlp_controller, tests/golden/mlp_controller.json) -> torch layout [out][in].  The CNN controller's
+    checkpoint (tests/golden/cnn_controller.npz via load_controller: keys c1_w, c1_b, pi_logstd besides the MLP's) gives the CnnMlpPolicy weights."""
     g = lambda k: np.asarray(params[k], dtype=np.float32)
+    if "pi_logstd" in params and "logstd" not in params:
+        params = dict(params, logstd=params["pi_logstd"])
     out = {}
     if "vf_fc0_w" not in params:   # policy-only export (evaluation): a zero value network
         params = dict(params)
@@ -44,7 +53,45 @@ def weights_from_stable_baselines(params):
         out[net + "_w1"] = g(net + "_fc1_w").T.copy(); out[net + "_b1"] = g(net + "_fc1_b")
         out[net + "_w2"] = g(last + "_w").T.copy(); out[net + "_b2"] = g(last + "_b")
     out["log_std"] = g("logstd").reshape(-1) if "logstd" in params else np.zeros(out["pi_w2"].shape[0], np.float32)
+    if "c1_w" in params:   # CnnMlpPolicy (examples/models/cnn_controller): conv kernel [rows][1][1][n_filters], bias [1][n_filters][1][1]
+        w = g("c1_w")
+        out["c1_w"] = w.reshape(w.shape[0], w.shape[-1]).copy()
+        out["c1_b"] = g("c1_b").reshape(-1).copy()
     return out
+
+
+def load_controller(path):
+    """A converted stable-baselines checkpoint -> {"weights": {TF name: array}, "obs_rms": {"mean", "var", "count"}}: the MLP
+    controller's JSON (tests/golden/mlp_controller.json) or the CNN controller's arrays (tests/golden/cnn_controller.npz, keys
+    w_<name>, obs_rms_<field>; obs_rms mean / var keep the observation's shape)."""
+    if not str(path).endswith(".npz"):
+        import json
+        with open(path) as f:
+            return json.load(f)
+    z = np.load(path)
+    return {"weights": {k[2:]: z[k] for k in z.files if k.startswith("w_")},
+            "obs_rms": {k: z["obs_rms_" + k] for k in ("mean", "var", "count")}}
+
+
+def module_from_weights(w, obs_shape=None):
+    """The inverse of weights_from_module: a torch MlpPolicy, or a CnnMlpPolicy when `w` holds c1_w (obs_shape (rows,
+    features); default rows = c1_w's, features = pi_w0's inputs / n_filters), with these weights."""
+    import torch
+    from .rollout import CnnMlpPolicy, MlpPolicy
+    t = lambda k: torch.as_tensor(np.asarray(w[k], dtype=np.float32))
+    if "c1_w" in w:
+        rows, nf = np.asarray(w["c1_w"]).shape
+        net = CnnMlpPolicy(obs_shape or (rows, np.asarray(w["pi_w0"]).shape[1] // nf), n_filters=nf, act_dim=np.asarray(w["pi_w2"]).shape[0])
+    else:
+        net = MlpPolicy(np.asarray(w["pi_w0"]).shape[1], act_dim=np.asarray(w["pi_w2"]).shape[0])
+    with torch.no_grad():
+        if "c1_w" in w:
+            net.conv.weight.copy_(t("c1_w")); net.conv.bias.copy_(t("c1_b"))
+        for name in ("pi", "vf"):
+            for i, m in enumerate([m for m in getattr(net, name) if isinstance(m, nn.Linear)]):
+                m.weight.copy_(t("{}_w{}".format(name, i))); m.bias.copy_(t("{}_b{}".format(name, i)))
+        net.log_std.copy_(t("log_std"))
+    return net
 
 
 class DeviceActor(object):
@@ -64,6 +111,7 @@ class DeviceActor(object):
         self._configure()
         self.seed(seed, env_id_base)
         self._observed = False     # batch moments of the current observation already accumulated?
+        self.cnn = False           # conv front end loaded (load_policy with c1_w)?
 
     @classmethod
     def for_env(cls, vec, **kw):
@@ -94,16 +142,30 @@ class DeviceActor(object):
         nat.check(self._lib, self._lib.fwg_actor_seed(self._handle, int(seed) & (2 ** 64 - 1), int(env_id_base)))
 
     def load_policy(self, weights):
-        """`weights`: the torch MlpPolicy module, or a dict with the keys pi_w0 .. vf_b2, log_std (torch Linear layout)."""
+        """`weights`: the torch MlpPolicy / CnnMlpPolicy module, or a dict with the keys pi_w0 .. vf_b2, log_std (torch Linear
+        layout) and, for the CNN head, c1_w [rows][n_filters], c1_b [n_filters].  The architecture comes from the weights: with
+        c1_w the head runs the conv front end (fwg_actor_set_conv), without it the MLP on the flattened observation."""
         w = weights if isinstance(weights, dict) else weights_from_module(weights)
         keep, st = [], nat.ActorWeights()
-        shapes = {"pi_w0": (64, self.obs_dim), "pi_w1": (64, 64), "pi_w2": (self.act_dim, 64), "vf_w0": (64, self.obs_dim),
+        in0 = self.obs_dim
+        if "c1_w" in w:
+            cw = np.ascontiguousarray(np.asarray(w["c1_w"], dtype=np.float32))
+            cb = np.ascontiguousarray(np.asarray(w["c1_b"], dtype=np.float32).reshape(-1))
+            if cw.ndim != 2 or cb.shape != (cw.shape[1],):
+                raise ValueError("c1_w / c1_b: shapes {} / {}, want [rows][n_filters] / [n_filters]".format(cw.shape, cb.shape))
+            rows, nf = cw.shape
+            nat.check(self._lib, self._lib.fwg_actor_set_conv(self._handle, nf, rows, cw.ctypes.data, cb.ctypes.data))
+            in0 = nf * (self.obs_dim // rows)
+        else:
+            nat.check(self._lib, self._lib.fwg_actor_set_conv(self._handle, 0, 0, None, None))
+        self.cnn = "c1_w" in w
+        shapes = {"pi_w0": (64, in0), "pi_w1": (64, 64), "pi_w2": (self.act_dim, 64), "vf_w0": (64, in0),
                   "vf_w1": (64, 64), "vf_w2": (1, 64), "pi_b0": (64,), "pi_b1": (64,), "pi_b2": (self.act_dim,),
                   "vf_b0": (64,), "vf_b1": (64,), "vf_b2": (1,), "log_std": (self.act_dim,)}
         for k in _KEYS:
             a = np.ascontiguousarray(np.asarray(w[k], dtype=np.float32))
             if a.shape != shapes[k]:
-                raise ValueError("{}: shape {} but the 64-64 MlpPolicy needs {}".format(k, a.shape, shapes[k]))
+                raise ValueError("{}: shape {} but the 64-64 networks need {}".format(k, a.shape, shapes[k]))
             keep.append(a)
             setattr(st, k, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
         nat.check(self._lib, self._lib.fwg_actor_set_weights(self._handle, ctypes.byref(st)))

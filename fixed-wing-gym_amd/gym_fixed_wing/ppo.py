@@ -7,7 +7,8 @@ script does with `PPO2(MlpPolicy, VecNormalize(SubprocVecEnv(...))).learn(total_
   advantages  fwg_gae (HIP, one launch over the rollout buffers, 17 B per transition);
   update      the clipped-surrogate objective of stable-baselines' PPO2 with its defaults (gamma 0.99, lambda 0.95, clip 0.2 on
               policy AND value, entropy 0.01, value 0.5, lr 2.5e-4 Adam eps 1e-5, 4 epochs x 4 minibatches, gradient norm 0.5) --
-              torch autograd on the 12-64-64 networks by default; PPO(update="hip") runs it as HIP kernels instead
+              torch autograd on the 12-64-64 networks (or the CnnMlpPolicy: conv + 36-64-64) by default; PPO(update="hip") runs
+              the MlpPolicy's as HIP kernels instead
               (learner.HipLearner: forward / backward on the matrix cores, clip and Adam on the device, one captured graph
               per update, the head repacked on the device);
   curriculum  distributed.gather_success (one RCCL all-gather of 64 B per rank) + CurriculumSchedule after every rollout.
@@ -35,7 +36,13 @@ STAT_KEYS = ("pg_loss", "vf_loss", "entropy", "approx_kl", "clip_frac")
 
 def sb_init_(policy):
     """stable-baselines' MlpPolicy initialisation: orthogonal, gain sqrt(2) on the hidden layers, 0.01 on the action mean,
-    1 on the value output; zero biases; log-std 0 (common/policies.py mlp_extractor / linear(init_scale))."""
+    1 on the value output; zero biases; log-std 0 (common/policies.py mlp_extractor / linear(init_scale)).  A CnnMlpPolicy's
+    conv: orthogonal over its [rows][n_filters] kernel (SB2's conv helper: ortho_init of the kernel flattened to [rows x 1 x 1]
+    [n_filters]), zero bias, gain sqrt(2) -- the gain SB2's own CNN extractor (nature_cnn) passes; the fork's is not recorded."""
+    conv = getattr(policy, "conv", None)
+    if conv is not None:
+        nn.init.orthogonal_(conv.weight, gain=math.sqrt(2.0))
+        nn.init.zeros_(conv.bias)
     for net, out_gain in ((policy.pi, 0.01), (policy.vf, 1.0)):
         lin = [m for m in net if isinstance(m, nn.Linear)]
         for i, m in enumerate(lin):
@@ -78,7 +85,8 @@ def ppo_loss(policy, obs, actions, old_values, old_logp, adv, returns, cliprange
 
 
 class PPO(object):
-    """PPO2-style learner for a FixedWingVecEnv with vector observations (MlpPolicy).  `learn(total_timesteps)` alternates
+    """PPO2-style learner for a FixedWingVecEnv: MlpPolicy on the (flattened) observation by default, or
+    policy=CnnMlpPolicy(...) on 5 x 12 matrix observations (train_rl_controller.py --policy CNN; torch update path).  `learn(total_timesteps)` alternates
     rollouts of n_steps x num_envs transitions with noptepochs x nminibatches gradient steps; `callback(self, info)` runs after
     every update (the reference's monitor_training)."""
 
@@ -92,6 +100,8 @@ class PPO(object):
         hp.update(kw)
         if update not in ("torch", "hip"):
             raise ValueError("update must be 'torch' or 'hip', not {!r}".format(update))
+        if update == "hip" and getattr(policy, "conv", None) is not None:
+            raise ValueError("PPO(update='hip') has no backward pass through the conv of a CnnMlpPolicy: use update='torch'")
         self.update_path = update
         self.hp, self.vec, self.group = hp, vec, group
         self.n_steps = int(hp["n_steps"])

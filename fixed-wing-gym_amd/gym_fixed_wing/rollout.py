@@ -86,6 +86,57 @@ class MlpPolicy(nn.Module):
         return action, value, logp
 
 
+# The CNN controller's two unrecorded choices, settled against its published closed-loop rewards (tools/cnn_trace.py,
+# profiles/cnn_architecture.txt): tanh after the conv, feature-major flatten (TF's NHWC reshape).  The HIP head has the same two
+# as FWG_CNN_ACTIVATION / FWG_CNN_FEATURE_MAJOR (csrc/fwgym_actor.h).
+CNN_ACTIVATION = "tanh"
+CNN_FLATTEN = "nhwc"
+_CNN_ACT = {"identity": lambda z: z, "tanh": torch.tanh, "relu": torch.relu}
+
+
+class CnnFront(nn.Module):
+    """The conv of the reference's CnnMlpPolicy (examples/train_rl_controller.py:179-197, --policy CNN): the (rows, features)
+    observation through n_filters VALID kernels of rows x 1 (output height 1, shared by every feature), tanh, flattened
+    feature-major -> rows-free vector of features * n_filters.  weight [rows][n_filters] (TF kernel [rows][1][1][n_filters])."""
+
+    def __init__(self, obs_shape=(5, 12), n_filters=3):
+        super().__init__()
+        self.rows, self.features = int(obs_shape[0]), int(obs_shape[1])
+        self.n_filters = int(n_filters)
+        self.weight = nn.Parameter(torch.zeros(self.rows, self.n_filters))
+        self.bias = nn.Parameter(torch.zeros(self.n_filters))
+
+    @property
+    def out_dim(self):
+        return self.features * self.n_filters
+
+    def forward(self, obs):
+        x = obs.reshape(obs.shape[0], self.rows, self.features)
+        y = _CNN_ACT[CNN_ACTIVATION](torch.einsum("brj,rc->bjc", x, self.weight) + self.bias)   # [B][features][filters]
+        if CNN_FLATTEN != "nhwc":
+            y = y.transpose(1, 2)
+        return y.reshape(obs.shape[0], -1)                                                    # k = j * n_filters + c
+
+
+class CnnMlpPolicy(nn.Module):
+    """The CNN controller's policy (examples/models/cnn_controller): one conv shared by pi and vf (CnnFront), then the
+    MlpPolicy's separate 64-64 tanh networks on its 36 outputs.  Same contract as MlpPolicy: `pi(obs)` -> mean, `vf(obs)` ->
+    value, `log_std`; obs [N, rows * features] or [N, rows, features]."""
+
+    def __init__(self, obs_shape=(5, 12), n_filters=3, act_dim=3, hidden=64):
+        super().__init__()
+        self.obs_shape = (int(obs_shape[0]), int(obs_shape[1]))
+        self.conv = CnnFront(obs_shape, n_filters)
+        k = self.conv.out_dim
+        self.pi = nn.Sequential(self.conv, nn.Linear(k, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(),
+                                nn.Linear(hidden, act_dim))
+        self.vf = nn.Sequential(self.conv, nn.Linear(k, hidden), nn.Tanh(), nn.Linear(hidden, hidden), nn.Tanh(),
+                                nn.Linear(hidden, 1))
+        self.log_std = nn.Parameter(torch.zeros(act_dim))
+
+    act = MlpPolicy.act
+
+
 def collect_rollout(vec, policy, norm, n_steps, obs=None):
     """n_steps of policy inference + env step for all envs, everything on the device.  Returns the rollout buffer
     {obs, actions, values, logp, rewards, dones} ([n_steps, N, ...]) and the last normalised observation."""

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FWG_ABI_VERSION 21
+#define FWG_ABI_VERSION 22
 
 #define FWG_N_VARS 23        /* simulator variables, see fwg_var */
 #define FWG_N_RESET_VARS 21  /* the keys of reset(state=...) records (fixed_wing.py:287,308; test-set format) */
@@ -395,7 +395,8 @@ int fwg_replay_check(const fwg_handle* h, int capture_parity);
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct fwg_actor fwg_actor;
 
-/* Row-major float32 host arrays in torch.nn.Linear layout (weight [out][in], bias [out]); hidden width is 64. */
+/* Row-major float32 host arrays in torch.nn.Linear layout (weight [out][in], bias [out]); hidden width is 64.  A CNN head
+ * (fwg_actor_set_conv) takes the conv's n_filters x features outputs in layer 0: pi_w0 / vf_w0 are [64][n_filters * features]. */
 typedef struct fwg_actor_weights {
     const float *pi_w0, *pi_b0, *pi_w1, *pi_b1, *pi_w2, *pi_b2;   /* [64][obs_dim],[64],[64][64],[64],[act_dim][64],[act_dim] */
     const float *vf_w0, *vf_b0, *vf_w1, *vf_b1, *vf_w2, *vf_b2;   /* ... [1][64],[1] */
@@ -414,6 +415,18 @@ int fwg_actor_create(int device, int64_t n_envs, int obs_dim, int act_dim, float
                      float clip_reward, float epsilon, fwg_actor** out);
 void fwg_actor_destroy(fwg_actor* a);
 int fwg_actor_set_weights(fwg_actor* a, const fwg_actor_weights* w_host);
+/* CNN front end: the CnnMlpPolicy of the reference's CNN controller (examples/train_rl_controller.py:179-197, --policy CNN;
+ * shipped as examples/models/cnn_controller, policy_kwargs {n_filters: 3}, observation Box(5, 12)).  The normalised observation,
+ * taken as `rows` x features (features = obs_dim / rows, row-major: VecNormalize's order and the env's row log), passes one
+ * VALID conv whose kernel spans the whole window and one feature (output height 1), shared by pi and vf:
+ *     y[j][c] = tanh(b[c] + sum_r w[r][c] x[r][j]),  layer 0 input k = j * n_filters + c  (TF's NHWC flatten)
+ * w [rows][n_filters] (the TF kernel [rows][1][1][n_filters]), b [n_filters]; then fwg_actor_set_weights with [64][n_filters *
+ * features] layer-0 weights.  Refused (FWG_ERR_INVALID, fwg_last_error): non-matrix observations (rows < 2 or obs_dim not a
+ * multiple of rows), rows other than the observation length of the row log set with fwg_actor_set_obs_log (the conv spans the
+ * whole window), n_filters x features > 64, and any geometry other than 5 x 12 x 3 filters (the kernel instance of this build).
+ * n_filters = 0 switches back to the MLP on the flattened observation.  fwg_rollout_available() is 0 for a CNN head (the
+ * one-launch step runs the MLP head only) and fwg_learner_create refuses it (no backward pass through the conv). */
+int fwg_actor_set_conv(fwg_actor* a, int n_filters, int rows, const float* w_host, const float* b_host);
 int fwg_actor_set_stats(fwg_actor* a, const fwg_actor_stats* s_host, void* stream);
 int fwg_actor_get_stats(fwg_actor* a, fwg_actor_stats* s_host, void* stream);   /* synchronises the stream */
 /* training != 0: fwg_actor_act folds the batches seen by fwg_actor_observe into the running statistics (VecNormalize
