@@ -30,26 +30,28 @@ def _emu():
     return nat.load_library(build_emu()), HostBackend()
 
 
-def _policy(D, seed):
+def _policy(D, seed, A=3):
     torch.manual_seed(seed)
-    pol = sb_init_(MlpPolicy(D))
+    pol = sb_init_(MlpPolicy(D, act_dim=A))
     with torch.no_grad():
-        pol.log_std.copy_(torch.tensor([-0.4, 0.3, -0.9]))
+        pol.log_std.copy_(torch.tensor([-0.4, 0.3, -0.9, 0.1][:A]))
         pol.pi[-1].weight.mul_(40.0)     # means of order 1: ratios away from 1
     return pol
 
 
-def _batch(pol, n, D, seed):
-    """A batch whose rows all sit >= 1e-3 away from a clip boundary and from a tie of either max (float64 decisions)."""
+def _batch(pol, n, D, seed, ret_shift=0.0):
+    """A batch whose rows all sit >= 1e-3 away from a clip boundary and from a tie of either max (float64 decisions); as many
+    actions as `pol` has.  `ret_shift`: the returns' mean offset from the values (0: the value gradient is noise)."""
+    A = pol.log_std.numel()
     g = torch.Generator().manual_seed(seed)
     obs = torch.randn(n, D, generator=g, dtype=torch.float64) * 1.5
-    act = torch.randn(n, 3, generator=g, dtype=torch.float64) * 0.8
+    act = torch.randn(n, A, generator=g, dtype=torch.float64) * 0.8
     adv = torch.randn(n, generator=g, dtype=torch.float64) * 2 + 0.3
     pol64 = copy.deepcopy(pol).double()
     with torch.no_grad():
         mean, v = pol64.pi(obs), pol64.vf(obs).squeeze(-1)
         ls = pol64.log_std
-        neglogp = 0.5 * (((act - mean) / ls.exp()) ** 2).sum(-1) + 0.5 * math.log(2 * math.pi) * 3 + ls.sum()
+        neglogp = 0.5 * (((act - mean) / ls.exp()) ** 2).sum(-1) + 0.5 * math.log(2 * math.pi) * A + ls.sum()
 
     def away(x, pts, eps=1e-3):
         return torch.stack([(x - p).abs() >= eps for p in pts]).all(0)
@@ -61,7 +63,7 @@ def _batch(pol, n, D, seed):
         k = int(todo.sum())
         ratio[todo] = 0.6 + 0.8 * torch.rand(k, generator=g, dtype=torch.float64)
         d[todo] = torch.rand(k, generator=g, dtype=torch.float64) - 0.5
-        ret[todo] = v[todo] + 1.5 * torch.randn(k, generator=g, dtype=torch.float64)
+        ret[todo] = v[todo] + ret_shift + 1.5 * torch.randn(k, generator=g, dtype=torch.float64)
         vc = v - d + d.clamp(-CLIP, CLIP)
         l1, l2 = (v - ret) ** 2, (vc - ret) ** 2
         ok = away(ratio, [1 - CLIP, 1 + CLIP]) & away(d, [-CLIP, CLIP]) & (((l1 - l2).abs() >= 1e-3) | (d.abs() <= CLIP))
@@ -81,14 +83,15 @@ def _ref_grad(pol, b):
     st = {k: float(v) for k, v in st.items()}
     with torch.no_grad():   # (the policy loss is a mean of terms of both signs: its tolerance is relative to their magnitude)
         a = (d["adv"] - d["adv"].mean()) / (d["adv"].std(unbiased=False) + 1e-8)
-        neglogp = 0.5 * (((d["actions"] - p64.pi(d["obs"])) / p64.log_std.exp()) ** 2).sum(-1) + 0.5 * math.log(2 * math.pi) * 3 + p64.log_std.sum()
+        neglogp = 0.5 * (((d["actions"] - p64.pi(d["obs"])) / p64.log_std.exp()) ** 2).sum(-1) + \
+            0.5 * math.log(2 * math.pi) * p64.log_std.numel() + p64.log_std.sum()
         ratio = torch.exp(-d["logp"] - neglogp)
         st["pg_scale"] = float(torch.max(-a * ratio, -a * ratio.clamp(1 - CLIP, 1 + CLIP)).abs().mean())
     return [p.grad.detach() for p in p64.parameters()], st
 
 
 def _learner(lib, mem, pol, device):
-    actor = DeviceActor(4, pol.pi[0].in_features, _backend=mem, _lib=lib)
+    actor = DeviceActor(4, pol.pi[0].in_features, act_dim=pol.log_std.numel(), _backend=mem, _lib=lib)
     L = HipLearner(lib, actor, pol, device, graph=False)
     L.set_hparams(2.5e-4, CLIP, ENT, VF, MAXN)
     return L, actor

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Do the oracle tests notice a known bug?  Puts the terminal-observation bugs that lived in the kernels through rounds 1-5 back into
+"""Do the tests notice a known bug?  Puts the terminal-observation bugs that lived in the kernels through rounds 1-5 back into
 a COPY of csrc/ (the fixes were commits b1ce333 and 8b54a4a, and round 6's log_plane fix), builds it, and runs the round-6 coverage
-tests against the mutant: every mutant must be caught ("What's weak" 2 / "Next round" 1).
+tests against the mutant: every mutant must be caught ("What's weak" 2 / "Next round" 1).  The learner mutants
+(the PPO update, fwgym_learner.h) are plausible slips of a rewrite of its kernels; they run the emulated forms of
+tests/test_ppo_hip_contract.py.
 
-    python tools/mutation_check.py emu                 # host emulation: the steady-state sampled test and the fuzzer, here
+    python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a gpurun session:
                                                        # FWGYM_MUTANT_LIB=... python -m pytest tests/test_gpu_oracle_coverage.py
 
@@ -35,7 +37,32 @@ MUTANTS = {
     "log_plane_past_the_log": [
         ("fwgym_env.h", "    return (long long)p * L + home + ((wraps > 0 && home <= len - 2) ? (long long)P * wraps : 0);",
          "    return (long long)p * L + home + (long long)P * wraps;")],
+    # the PPO update: the minibatch's rows read in buffer order instead of through the permutation
+    "ppo_gather_ignores_idx": [
+        ("fwgym_learner.h", "            const long long row = ok ? G.idx[r0 + r] : 0;",
+         "            const long long row = ok ? (long long)(r0 + r) : 0;")],
+    # the rows of a tail tile past the minibatch counted in the loss terms
+    "ppo_loss_tail_unmasked": [
+        ("fwgym_learner.h", "                const bool ok = r < nrows;\n                const float* rf = rowf + r * 8;",
+         "                const bool ok = true;\n                const float* rf = rowf + r * 8;")],
+    # the last workgroup's partial gradient left out of the sum
+    "ppo_reduce_drops_a_slab": [
+        ("fwgym_learner.h", "    for (int b = 0; b < nslab; ++b) s += slab[(size_t)b * L.SW + j];",
+         "    for (int b = 0; b < nslab - 1; ++b) s += slab[(size_t)b * L.SW + j];")],
+    # the advantages normalised by the unbiased std (PPO2 and ppo_loss take the biased one)
+    "ppo_moments_unbiased_std": [
+        ("fwgym_learner.h", "        mom[2 * blockIdx.x + 1] = (float)sqrt(red[0] / (double)mb) + 1e-8f;",
+         "        mom[2 * blockIdx.x + 1] = (float)sqrt(red[0] / (double)(mb - 1)) + 1e-8f;")],
+    # the head repacked on the device without the low bf16 parts of the weights
+    "actor_pack_zero_low_parts": [
+        ("fwgym_learner.h", "        frags[((net * 2 + 1) * nfw + f) * 64 + l] = frag_t{wl[0], wl[1], wl[2], wl[3]};",
+         "        frags[((net * 2 + 1) * nfw + f) * 64 + l] = frag_t{0u, 0u, 0u, 0u};")],
 }
+_ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
+                 os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
+_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_contract.py")]
+# the pytest arguments each mutant runs in `emu` mode
+TESTS = {name: (_LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _ORACLE_TESTS) for name in MUTANTS}
 
 
 def mutated_tree(name):
@@ -86,11 +113,10 @@ def main():
         return 0
     sys.path[:0] = [ROOT, os.path.join(ROOT, "fixed-wing-gym_amd"), os.path.join(ROOT, "tests")]
     caught = {}
-    for name in MUTANTS:
+    for name in (sys.argv[2:] or MUTANTS):
         d, dst = mutated_tree(name)
         env = dict(os.environ, FWGYM_MUTANT_SRC=dst, FWGYM_MUTANT_TAG="_mut_" + name)
-        r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "-k", "not frozen_kernel_through",
-                            os.path.join(ROOT, "tests", "test_emu_coverage.py"), os.path.join(ROOT, "tests", "test_emu_fuzz.py")],
+        r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider"] + TESTS[name],
                            env=env, capture_output=True, text=True)
         caught[name] = r.returncode != 0
         tail = [l for l in r.stdout.splitlines() if "Mismatch" in l or "FAILED" in l or "passed" in l or "failed" in l][-6:]
