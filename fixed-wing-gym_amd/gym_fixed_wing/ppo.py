@@ -7,16 +7,17 @@ script does with `PPO2(MlpPolicy, VecNormalize(SubprocVecEnv(...))).learn(total_
   advantages  fwg_gae (HIP, one launch over the rollout buffers, 17 B per transition);
   update      the clipped-surrogate objective of stable-baselines' PPO2 with its defaults (gamma 0.99, lambda 0.95, clip 0.2 on
               policy AND value, entropy 0.01, value 0.5, lr 2.5e-4 Adam eps 1e-5, 4 epochs x 4 minibatches, gradient norm 0.5) --
-              torch autograd on the 12-64-64 networks (or the CnnMlpPolicy: conv + 36-64-64) by default; PPO(update="hip") runs
-              the MlpPolicy's as HIP kernels instead
-              (learner.HipLearner: forward / backward on the matrix cores, clip and Adam on the device, one captured graph
-              per update, the head repacked on the device);
+              by one of learner.py's two updaters, which share one update() interface: TorchUpdater (the default) is torch
+              autograd on the 12-64-64 networks (or the CnnMlpPolicy: conv + 36-64-64), each minibatch step one captured graph;
+              HipLearner (PPO(update="hip")) runs the MlpPolicy's as HIP kernels (forward / backward on the matrix cores, clip
+              and Adam on the device, one captured graph per update, the head repacked on the device);
   curriculum  distributed.gather_success (one RCCL all-gather of 64 B per rank) + CurriculumSchedule after every rollout.
 
-The torch policy is the master copy of the weights; after every update they are loaded into the HIP head
-(DeviceActor.load_policy; with update="hip" the parameters are views of the learner's flat device buffer and the head is
-repacked on the device).  Multi-GPU: every rank collects its shard; gradients are averaged with one all-reduce per
-minibatch step when torch.distributed is initialised (data-parallel PPO)."""
+PPO is the training loop and the policy of an update (hyper-parameters, permutations, minibatch split); a step's mechanics are
+the updater's (PPO.learner).  The torch policy is the master copy of the weights; the updater leaves them in the HIP head after
+every update (DeviceActor.load_policy; with update="hip" the parameters are views of the learner's flat device buffer and the head
+is repacked on the device).  Multi-GPU: every rank collects its shard; gradients are averaged with one all-reduce per minibatch
+step when torch.distributed is initialised (data-parallel PPO)."""
 import math
 
 import numpy as np
@@ -24,14 +25,12 @@ import torch
 from torch import nn
 
 from . import _native as nat
+from .learner import STAT_KEYS, HipLearner, TorchUpdater, ppo_loss  # noqa: F401  (STAT_KEYS, ppo_loss: re-exported)
 from .rollout import FusedRollout, MlpPolicy
 
 # stable-baselines PPO2.__init__ defaults (the reference passes none: `PPO2(policy, env, verbose=1, tensorboard_log=...)`)
 PPO2_DEFAULTS = dict(gamma=0.99, n_steps=128, ent_coef=0.01, learning_rate=2.5e-4, vf_coef=0.5, max_grad_norm=0.5, lam=0.95,
                      nminibatches=4, noptepochs=4, cliprange=0.2)
-
-
-STAT_KEYS = ("pg_loss", "vf_loss", "entropy", "approx_kl", "clip_frac")
 
 
 def sb_init_(policy):
@@ -64,26 +63,6 @@ def gae(lib, mem, rewards, values, dones, last_value, gamma, lam, adv_out=None, 
     return adv_out, ret_out
 
 
-def ppo_loss(policy, obs, actions, old_values, old_logp, adv, returns, cliprange, ent_coef, vf_coef):
-    """PPO2's loss on one minibatch (stable-baselines ppo2.py setup_model): advantages normalised per minibatch, clipped
-    surrogate, value loss clipped around the old value with the SAME range, Gaussian entropy bonus."""
-    adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
-    mean = policy.pi(obs)
-    value = policy.vf(obs).squeeze(-1)
-    log_std = policy.log_std
-    neglogp = 0.5 * (((actions - mean) / log_std.exp()) ** 2).sum(dim=-1) + 0.5 * math.log(2.0 * math.pi) * actions.shape[-1] + log_std.sum()
-    ratio = torch.exp(-old_logp - neglogp)
-    pg_loss = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - cliprange, 1.0 + cliprange)).mean()
-    v_clipped = old_values + torch.clamp(value - old_values, -cliprange, cliprange)
-    vf_loss = 0.5 * torch.max((value - returns) ** 2, (v_clipped - returns) ** 2).mean()
-    entropy = (log_std + 0.5 * math.log(2.0 * math.pi * math.e)).sum()
-    loss = pg_loss - ent_coef * entropy + vf_coef * vf_loss
-    with torch.no_grad():
-        stats = {"pg_loss": pg_loss.detach(), "vf_loss": vf_loss.detach(), "entropy": entropy.detach(),
-                 "approx_kl": 0.5 * ((neglogp + old_logp) ** 2).mean(), "clip_frac": ((ratio - 1.0).abs() > cliprange).float().mean()}
-    return loss, stats
-
-
 class PPO(object):
     """PPO2-style learner for a FixedWingVecEnv: MlpPolicy on the (flattened) observation by default, or
     policy=CnnMlpPolicy(...) on 5 x 12 matrix observations (train_rl_controller.py --policy CNN; torch update path).  `learn(total_timesteps)` alternates
@@ -102,7 +81,6 @@ class PPO(object):
             raise ValueError("update must be 'torch' or 'hip', not {!r}".format(update))
         if update == "hip" and getattr(policy, "conv", None) is not None:
             raise ValueError("PPO(update='hip') has no backward pass through the conv of a CnnMlpPolicy: use update='torch'")
-        self.update_path = update
         self.hp, self.vec, self.group = hp, vec, group
         self.n_steps = int(hp["n_steps"])
         self._torch_dev = getattr(vec._mem, "device", torch.device("cpu"))
@@ -113,15 +91,10 @@ class PPO(object):
         self._rollout_kw = dict(graph=bool(graph) and self._torch_dev.type == "cuda", fused=fused)
         self.rollout = FusedRollout(vec, self.actor, self.n_steps, **self._rollout_kw)
         self._spec_at_capture = vec.spec_index
-        on_gpu = self._torch_dev.type == "cuda"
-        if update == "hip":   # (the module's parameters become views of the learner's flat buffer; no torch optimiser)
-            from .learner import HipLearner
-            self.opt, self._lr = None, hp["learning_rate"]
-            self.learner = HipLearner(vec._lib, self.actor, self.policy, self._torch_dev, graph=bool(graph_update) and on_gpu)
+        if update == "hip":   # (the module's parameters become views of its flat buffer here, before the broadcast below writes through them)
+            self.learner = HipLearner(vec._lib, self.actor, self.policy, self._torch_dev, graph=graph_update, lr=hp["learning_rate"])
         else:
-            # (GPU: the fused, capturable form -- ONE launch for all thirteen parameter tensors inside the captured minibatch step)
-            self.opt = torch.optim.Adam(self.policy.parameters(), lr=hp["learning_rate"], eps=1e-5, **({"capturable": True, "fused": True} if on_gpu else {}))
-        self._graph_update, self._step_graph = bool(graph_update) and on_gpu, None
+            self.learner = TorchUpdater(self.actor, self.policy, self._torch_dev, graph=graph_update, lr=hp["learning_rate"])
         self.curriculum = curriculum
         m, N, T = vec._mem, vec.num_envs, self.n_steps
         self.adv, self.ret = m.zeros((T, N)), m.zeros((T, N))
@@ -136,9 +109,6 @@ class PPO(object):
                 torch.distributed.broadcast(p.data, src=0, group=group)
             self.actor.load_policy(self.policy)
 
-    def _t(self, x):
-        return torch.as_tensor(x) if not isinstance(x, torch.Tensor) else x
-
     def collect(self):
         """One rollout + advantages.  Returns the flattened training batch (views of the rollout buffers, no copies)."""
         buf = self.rollout.run()
@@ -146,120 +116,19 @@ class PPO(object):
             self.hp["gamma"], self.hp["lam"], self.adv, self.ret)
         T, N = self.n_steps, self.vec.num_envs
         self.num_timesteps += T * N * self._world
-        flat = lambda x, *s: self._t(x).reshape((T * N,) + s)
+        flat = lambda x, *s: torch.as_tensor(x).reshape((T * N,) + s)
         return {"obs": flat(buf["obs"], self.vec.obs_dim), "actions": flat(buf["actions"], 3), "values": flat(buf["values"]),
                 "logp": flat(buf["logp"]), "adv": flat(self.adv), "returns": flat(self.ret)}
 
-    def _minibatch_step(self, mbatch, cliprange):
+    def update(self, batch, lr=None, cliprange=None):
+        """noptepochs x nminibatches steps on `batch` by the updater; a given `lr` stays in force.  Returns the steps' mean statistics."""
         hp = self.hp
-        loss, stats = ppo_loss(self.policy, mbatch["obs"], mbatch["actions"], mbatch["values"], mbatch["logp"], mbatch["adv"],
-                               mbatch["returns"], cliprange, hp["ent_coef"], hp["vf_coef"])
-        self.opt.zero_grad(set_to_none=False)
-        loss.backward()
-        if self._world > 1:   # data-parallel PPO: one all-reduce of the (tiny) gradient per minibatch step
-            flat = torch.cat([p.grad.reshape(-1) for p in self.policy.parameters()])
-            torch.distributed.all_reduce(flat, group=self.group)
-            flat /= self._world
-            o = 0
-            for p in self.policy.parameters():
-                p.grad.copy_(flat[o:o + p.numel()].view_as(p))
-                o += p.numel()
-        nn.utils.clip_grad_norm_(self.policy.parameters(), hp["max_grad_norm"])
-        self.opt.step()
-        return torch.stack([stats[k] for k in STAT_KEYS])
-
-    def _capture_step(self, batch, mb, cliprange):
-        """One minibatch step -- gather by index, loss, backward, gradient clipping, Adam -- as ONE hipGraph: the 12-64-64
-        networks make it ~60 launches of microseconds each, and issued from Python they cost 1.5 ms per step (99 % of a training
-        run at 4 096 envs was the optimiser waiting for its own launches)."""
-        dev = self._torch_dev
-        g = {"idx": torch.zeros(mb, dtype=torch.long, device=dev), "acc": torch.zeros(len(STAT_KEYS), device=dev), "src": batch,
-             "key": (tuple(int(batch[k].data_ptr()) for k in sorted(batch)), mb, float(cliprange))}
-        snap_p = [p.detach().clone() for p in self.policy.parameters()]
-        snap_o = [{k: v.clone() for k, v in st.items() if isinstance(v, torch.Tensor)} for st in self.opt.state.values()]
-
-        # ONE gather per step: the six per-transition arrays side by side in a [n, D + 7] buffer, refreshed once per update
-        D = batch["obs"].shape[1]
-        g["packed"] = torch.empty((batch["obs"].shape[0], D + 7), device=dev)
-        g["pack"] = lambda: torch.cat([batch["obs"], batch["actions"], batch["values"][:, None], batch["logp"][:, None],
-                                       batch["adv"][:, None], batch["returns"][:, None]], dim=1, out=g["packed"])
-        g["pack"]()
-
-        def body():
-            m = g["packed"].index_select(0, g["idx"])
-            mbatch = {"obs": m[:, :D], "actions": m[:, D:D + 3], "values": m[:, D + 3], "logp": m[:, D + 4], "adv": m[:, D + 5],
-                      "returns": m[:, D + 6]}
-            g["acc"].add_(self._minibatch_step(mbatch, cliprange))
-
-        g["idx"].copy_(torch.arange(mb, device=dev))
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        had_state = len(snap_o) > 0
-        with torch.no_grad():   # the warm-up steps were real optimiser steps: put weights and moments back IN PLACE
-            for p, q in zip(self.policy.parameters(), snap_p):
-                p.copy_(q)
-            for i, st in enumerate(self.opt.state.values()):
-                for k, v in st.items():
-                    if isinstance(v, torch.Tensor):
-                        v.copy_(snap_o[i][k]) if had_state else v.zero_()
-        g["graph"] = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g["graph"]):
-            body()
-        g["acc"].zero_()
-        return g
-
-    def _update_hip(self, batch, lr, cliprange):
-        """The same update on the HIP learner: the same permutations from the same generator calls as the torch path."""
-        hp = self.hp
-        n = batch["obs"].shape[0]
-        nmb = int(hp["nminibatches"])
-        if lr is not None:   # (as the torch path: a given lr stays in force)
-            self._lr = lr
-        perms = [torch.randperm(n, device=self._torch_dev, generator=self._gen) for _ in range(int(hp["noptepochs"]))]
-        stats = self.learner.update(batch, perms, n // nmb, nmb, self._lr, hp["cliprange"] if cliprange is None else cliprange,
+        n, nmb = batch["obs"].shape[0], int(hp["nminibatches"])
+        perms = (torch.randperm(n, device=self._torch_dev, generator=self._gen) for _ in range(int(hp["noptepochs"])))
+        stats = self.learner.update(batch, perms, n // nmb, nmb, lr, hp["cliprange"] if cliprange is None else cliprange,
                                     hp["ent_coef"], hp["vf_coef"], hp["max_grad_norm"], world=self._world, group=self.group)
         self.updates += 1
         return stats
-
-    def update(self, batch, lr=None, cliprange=None):
-        if self.update_path == "hip":
-            return self._update_hip(batch, lr, cliprange)
-        hp = self.hp
-        n = batch["obs"].shape[0]
-        mb = n // int(hp["nminibatches"])
-        cliprange = hp["cliprange"] if cliprange is None else cliprange
-        if lr is not None:
-            for g in self.opt.param_groups:
-                g["lr"] = lr
-        graphed = self._graph_update and self._world == 1 and lr is None
-        if graphed:
-            key = (tuple(int(batch[k].data_ptr()) for k in sorted(batch)), mb, float(cliprange))
-            if self._step_graph is None or self._step_graph["key"] != key:
-                self._step_graph = self._capture_step(batch, mb, cliprange)
-            sg = self._step_graph
-            sg["pack"]()
-            sg["acc"].zero_()
-        acc = torch.zeros(len(STAT_KEYS), device=self._torch_dev)
-        for _ in range(int(hp["noptepochs"])):
-            perm = torch.randperm(n, device=self._torch_dev, generator=self._gen)
-            for k in range(int(hp["nminibatches"])):
-                idx = perm[k * mb:(k + 1) * mb]
-                if graphed:
-                    sg["idx"].copy_(idx)
-                    sg["graph"].replay()
-                else:
-                    acc += self._minibatch_step({key_: v[idx] for key_, v in batch.items()}, cliprange)
-        if graphed:
-            acc = sg["acc"].clone()
-        steps = int(hp["noptepochs"]) * int(hp["nminibatches"])
-        self.actor.load_policy(self.policy)
-        self.updates += 1
-        return {k: float(v) / steps for k, v in zip(STAT_KEYS, acc.tolist())}
 
     def learn(self, total_timesteps, callback=None, log=None):
         from . import distributed as fd
