@@ -2381,8 +2381,9 @@ int fwg_replay_check(const fwg_handle* h, int capture_parity) {
                                           "parameter sets drawn under the old ranges (issue two direct fwg_step calls, then capture again)");
     if (h->spec != h->spec_at_capture)
         return fail_with(FWG_ERR_INVALID, "hipGraph captured before an fwg_update_config that moved the configuration to another kernel instance "
-                                          "(a frozen configuration's kernel has its values folded in: set_curriculum_level on a preset leaves "
-                                          "it for the shape instance): its launches would keep computing with the old values -- capture again");
+                                          "(a frozen configuration's kernel has its values folded in: an update of one of them, the turbulence "
+                                          "intensity for one, leaves it for the shape instance; set_curriculum_level does not, its ranges are "
+                                          "read from memory): its launches would keep computing with the old values -- capture again");
     if ((int)(h->gstep & 1) != (capture_parity & 1))
         return fail_with(FWG_ERR_INVALID, "hipGraph captured at the other step parity: its launches would read the stale copy of the ring "
                                           "positions (run an even number of direct steps between capture and replay, or capture again)");

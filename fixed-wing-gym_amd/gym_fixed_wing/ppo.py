@@ -144,8 +144,9 @@ class PPO(object):
             if self.curriculum is not None:
                 info["level"] = self.curriculum.update(self.vec, summary)
                 if self._rollout_kw["graph"] and self.vec.spec_index != self._spec_at_capture:
-                    # (a captured rollout holds a kernel INSTANCE; the curriculum's ranges are read from memory and do not move it,
-                    # but a configuration update that changes a folded value would: capture anew, fwg_replay_check refuses otherwise)
+                    # (a captured rollout holds a kernel INSTANCE; the curriculum's ranges are read from memory and do not move it --
+                    # a preset stays on its frozen kernel at every level, tests/test_shape_instance.py -- but a schedule whose
+                    # update changes a folded value would: capture anew, fwg_replay_check refuses otherwise)
                     self.rollout = FusedRollout(self.vec, self.actor, self.n_steps, **self._rollout_kw)
                     self._spec_at_capture = self.vec.spec_index
             self.history.append(info)

@@ -113,6 +113,56 @@ def test_training_loop_on_the_emulated_env():
     vec.close()
 
 
+def test_learn_captures_the_rollout_anew_exactly_when_the_kernel_instance_moves(monkeypatch):
+    """PPO.learn after CurriculumSchedule.update: a graphed rollout holds a kernel INSTANCE.  A level change leaves a frozen preset
+    on its kernel (tests/test_shape_instance.py) and the captured rollout goes on being replayed; an update of a folded value
+    moves the env to another instance, and the rollout is built anew.  Emulated env (the C3 preset on its frozen kernel), a
+    stubbed schedule, and FusedRollout constructions counted -- the graph flag is forced on, the rollouts built stay eager."""
+    from emu.host_backend import HostBackend, build_emu
+    from gym_fixed_wing import ppo as ppo_mod
+    from gym_fixed_wing.vec_env import FixedWingVecEnv
+    name, kind, ckw, skw = [c for c in configs.CASES if c[0] == "spec_c3"][0]
+    vec = FixedWingVecEnv(configs.reference_like(kind), num_envs=70, config_kw=ckw, sim_config_kw=skw, seed=3, _backend=HostBackend(),
+                          _lib_path=build_emu())
+    frozen = vec.spec_index
+    assert frozen >= 0
+    vec.set_curriculum_level(0.25)
+    vec.reset()
+    script = [lambda v: v.set_curriculum_level(0.57), lambda v: None, lambda v: v.set_simulator_attr("turbulence_intensity", "light"),
+              lambda v: v.set_curriculum_level(1.0), lambda v: v.set_simulator_attr("turbulence_intensity", "moderate"),
+              lambda v: v.set_curriculum_level(1.0)]
+    moves = [False, False, True, False, True, False]
+
+    class Schedule(object):
+        level = 0.25
+
+        def update(self, vec, summary):
+            script.pop(0)(vec)
+            return self.level
+
+    ppo = PPO(vec, seed=0, n_steps=4, nminibatches=2, noptepochs=1, curriculum=Schedule())
+    built, instances = [], []
+    real = ppo_mod.FusedRollout
+
+    def counting(v, actor, n_steps, graph=False, fused=None):
+        built.append(v.spec_index)
+        return real(v, actor, n_steps, graph=False, fused=fused)
+
+    monkeypatch.setattr(ppo_mod, "FusedRollout", counting)
+    ppo._rollout_kw["graph"] = True
+    taken = []
+
+    def after(p, info):
+        taken.append(len(built))
+        instances.append(p.vec.spec_index)
+
+    ppo.learn(len(moves) * 4 * 70, callback=after)
+    assert instances[:2] == [frozen, frozen] and instances[2] != frozen and instances[3] != frozen and instances[4:] == [frozen, frozen], instances
+    assert [b - a for a, b in zip([0] + taken[:-1], taken)] == [int(m) for m in moves], (taken, moves)
+    assert built == [instances[2], frozen]
+    vec.close()
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # the end-to-end check: a policy trained from random initialisation (GPU)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -54,6 +54,27 @@ def test_config_lands_on_the_right_tier():
         del os.environ["FWGYM_SHAPE"]
 
 
+@pytest.mark.parametrize("entry", presets.SPECIALISED, ids=[e[0] for e in presets.SPECIALISED])
+def test_curriculum_level_leaves_a_preset_on_its_frozen_kernel(entry):
+    """set_curriculum_level on a frozen preset -- examples/train_ppo.py starts "examples" (c5_examples_lean) and "cnn"
+    (ship_cnn_log) at level 0.25 and climbs to 1 -- rescales the init / target RANGES, which are kept out of the block a frozen
+    kernel has folded in (DynCfg, read from memory by every kernel): at every level the configuration lands on the frozen kernel
+    itself, never on its shape instance.  So fwg_replay_check's instance rule never fires on a level change, and PPO.learn's
+    re-capture branch does not run for one (tests/test_ppo.py)."""
+    name, kind, ckw, skw = entry
+    lib = nat.load_library()
+    rows = presets.OBS_LOG_ROWS if name.endswith("_log") else 0
+    want = [e[0] for e in presets.SPECIALISED].index(name)
+    got = {}
+    for level in (None, 0.25, 0.57, 1.0):
+        ec = EnvConfig(presets.preset(kind), config_kw=copy.deepcopy(ckw), sim_config_kw=copy.deepcopy(skw))
+        if level is not None:
+            ec.set_curriculum_level(level)
+        c = ec.compile(auto_reset=True, store_derived="_lean" not in name, obs_log_rows=rows)
+        got[level] = int(lib.fwg_config_instance(ctypes.byref(c)))
+    assert got == {None: want, 0.25: want, 0.57: want, 1.0: want}, (name, got)
+
+
 def test_emulation_build_has_no_shape_instances():
     from emu.host_backend import build_emu
     lib = nat.load_library(build_emu())

@@ -6,8 +6,8 @@ tests against the mutant: every mutant must be caught ("What's 
 tests/test_ppo_hip_contract.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
-    python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a gpurun session:
-                                                       # FWGYM_MUTANT_LIB=... python -m pytest tests/test_gpu_oracle_coverage.py
+    python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
+                                                       # FWGYM_MUTANT_LIB_ROW_LOG=... python -m pytest tests/test_gpu_oracle_coverage.py
 
 Never the product: the mutated sources live in a temporary directory."""
 import os
@@ -57,12 +57,38 @@ MUTANTS = {
     "actor_pack_zero_low_parts": [
         ("fwgym_learner.h", "        frags[((net * 2 + 1) * nfw + f) * 64 + l] = frag_t{wl[0], wl[1], wl[2], wl[3]};",
          "        frags[((net * 2 + 1) * nfw + f) * 64 + l] = frag_t{0u, 0u, 0u, 0u};")],
+    # ---- the tag (configuration generation, episode) on prepared reset draws: what keeps a draw of the old ranges out after
+    # set_curriculum_level.  The generation dropped from the two waves' decision whether a complete draw is used / installed
+    "draw_ready_ignores_generation": [
+        ("fwgym.hip", "        if (pre_install) pre_rows = pre_draw && f2u(pre_tag.x) == dc.generation && f2u(pre_tag.y) == E.episode + 1u;",
+         "        if (pre_install) pre_rows = pre_draw && f2u(pre_tag.y) == E.episode + 1u;"),
+        ("fwgym.hip", "                ready = pre_draw && f2u(pre_tag.x) == dc.generation && f2u(pre_tag.y) == E.episode + 1u;",
+         "                ready = pre_draw && f2u(pre_tag.y) == E.episode + 1u;")],
+    # ... from the check that discards the pieces of a half-prepared draw
+    "draw_piece_ignores_generation": [
+        ("fwgym_env.h", "        if (f2u(tag.x) != dc.generation || f2u(tag.y) != episode_new) stage = 0u;",
+         "        if (f2u(tag.y) != episode_new) stage = 0u;")],
+    # ... from the tags of the per-env aircraft constants and reward scalings (k_model_draw, k_model_draw_q)
+    "model_draw_ignores_generation": [
+        ("fwgym.hip", "        if (!(f2u(tag.x) == episode_new && f2u(tag.y) == dp->generation)) {", "        if (!(f2u(tag.x) == episode_new)) {"),
+        ("fwgym.hip", "    if (f2u(tag.y) == episode_new && f2u(tag.z) == dp->generation) return;", "    if (f2u(tag.y) == episode_new) return;"),
+        ("fwgym.hip", "        if (f2u(tag.y) == episode_new && f2u(tag.z) == dp->generation) continue;   // (wave-uniform)",
+         "        if (f2u(tag.y) == episode_new) continue;   // (wave-uniform)")],
+    # fwg_update_config leaves the generation where it is
+    "update_config_keeps_generation": [
+        ("fwgym.hip", "    dy.generation = h->hd.generation + 1u;   // ranges may have changed: prepared reset draws are stale",
+         "    dy.generation = h->hd.generation;")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
 _LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_contract.py")]
+# (the regime in which prepared draws are completed, and the seed change: the 45-step regime never holds a complete draw)
+_CURRICULUM_TESTS = ["-k", "sparse or another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
 # the pytest arguments each mutant runs in `emu` mode
-TESTS = {name: (_LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _ORACLE_TESTS) for name in MUTANTS}
+TESTS = {name: (_LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else
+                _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
+# (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
+TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
 
 
 def mutated_tree(name):
@@ -87,8 +113,13 @@ def _hip_mutant(job):
     cache = tempfile.mkdtemp(prefix="fwg_mutcache_")
     jit.CSRC, jit.CACHE = dst, cache
     cfg, ckw, skw, _, _ = presets.workload("c3")
-    ckw = dict(copy.deepcopy(ckw), steps_max=45, simulator={"states": {6: {"constraint_min": -60, "constraint_max": 60}}})
-    lib = jit.prebuild(cfg, ckw, skw, derived_views=False, obs_log_rows=presets.OBS_LOG_ROWS if layout == "row_log" else 0)
+    # (layout "curriculum" / "curriculum_model16": the row-log configurations of the curriculum runs of
+    # tests/test_gpu_oracle_coverage.py -- c3_sparse_log with its 181-step episodes, c3_model16_lean_log with per-env aircraft)
+    if layout == "curriculum_model16":
+        cfg = presets.preset("cnn_model16")
+    ckw = dict(copy.deepcopy(ckw), steps_max=181 if layout == "curriculum" else 45,
+               simulator={"states": {6: {"constraint_min": -60, "constraint_max": 60}}})
+    lib = jit.prebuild(cfg, ckw, skw, derived_views=False, obs_log_rows=0 if layout == "dense" else presets.OBS_LOG_ROWS)
     assert lib is not None, (name, layout)
     out = os.path.join(outdir, "libfwgym_mut_{}_{}.so".format(name, layout))
     shutil.move(lib, out)
@@ -107,6 +138,11 @@ def main():
         import copy
         from concurrent.futures import ProcessPoolExecutor
         jobs = [(name, layout, outdir) for name in ("airdata", "install_on_failed_last_step") for layout in ("row_log", "dense")]
+        # FWGYM_MUTANT_LIB_CURRICULUM / FWGYM_MUTANT_LIB_CURRICULUM_MODEL16 point the curriculum runs at these.  The first must be
+        # caught there (c3_sparse_log).  The second is EXPECTED TO SURVIVE c3_model16_lean_log: a level change moves no range the
+        # per-env sets are drawn from, so a set kept across it equals a new draw; only a seed change shows that mutant
+        # (tests/test_emu_curriculum.py, the `another_seed` tests).  It is built so that a GPU session can confirm this
+        jobs += [("draw_ready_ignores_generation", "curriculum", outdir), ("model_draw_ignores_generation", "curriculum_model16", outdir)]
         with ProcessPoolExecutor(max_workers=4) as pool:
             for out in pool.map(_hip_mutant, jobs):
                 print("built", out)
