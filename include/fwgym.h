@@ -390,8 +390,13 @@ int fwg_replay_check(const fwg_handle* h, int capture_parity);
  * (pi and vf: obs -> 64 tanh -> 64 tanh -> act_dim / 1, state-independent log-std) acting on the normalised
  * observation (examples/train_rl_controller.py:223-231, examples/evaluate_controller.py:93-100) -- as two HIP kernels
  * on device-resident batches, so that one rollout step is three launches (fwg_step, fwg_actor_observe, fwg_actor_act).
- * The MLP runs on the matrix cores (bf16 MFMA, each fp32 operand split into bf16 hi + lo: three products per tile,
- * error ~1e-5 of the fp32 result), weights resident in LDS.
+ * The MLP runs on the matrix cores (bf16 MFMA, each fp32 operand split into bf16 hi + lo: three products per tile), weights
+ * resident in LDS.  Precision of the split products, measured per element against float64 over obs_dim 1..64, act_dim 1..4 with
+ * weights that take tanh out of its linear range: mean and value within 3.7e-5 of max(|result|, 1) on the host emulation of the
+ * kernels, 4.9e-5 end to end for one-row batches (see fwg_actor_observe); profiles/actor_contract_errors.txt holds the tables per
+ * shape and machine (fp32 torch on the same inputs: 9e-7).  tests/test_actor_contract.py asserts twice the worst measured figure,
+ * and never more than 1e-4: one of the three products lost costs ~2^-9 of a term.  Single products (precise = 0): ~5e-3 of the
+ * largest output.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct fwg_actor fwg_actor;
 
@@ -445,7 +450,14 @@ int fwg_attach_observer(fwg_handle* h, fwg_actor* a);
  * sequences replay correctly).  NULL switches back to dense [N][obs_dim] batches.  The head keeps a plain pointer. */
 int fwg_actor_set_obs_log(fwg_actor* a, const fwg_handle* env);
 /* Accumulates the batch moments of `obs` ([N][obs_dim]) and, when `reward` is not NULL, advances the discounted
- * returns (ret = ret * gamma + reward, zeroed where `done`) and accumulates their moments (VecNormalize.step_wait). */
+ * returns (ret = ret * gamma + reward, zeroed where `done`) and accumulates their moments (VecNormalize.step_wait).
+ * Conditioning: the moments are sums of deviations from the running mean as it stood at the last fwg_actor_act (0 before the
+ * first), folded in fp32 as s2 - s1^2, so the relative error of the running variance grows with the square of the distance
+ * between a batch's mean and that running mean, in units of the batch's standard deviation:
+ *     <= 8 * 2^-24 * (1 + (mean / std)^2)   -- 4.8e-5 at a ratio of 10, 4.8e-3 at 100
+ * (the running mean itself stays within 2e-5).  The reference's VecNormalize is float64 and has no such limit; this env's
+ * observations stay below a ratio of about 10.  The batch sums travel as fixed-point integers of quantum 2^-20, which shows only
+ * for batches of a few rows: the mean of a one-row batch is off by up to 2^-21. */
 int fwg_actor_observe(fwg_actor* a, const float* obs, const float* reward, const uint8_t* done, void* stream);
 /* Folds the accumulated moments into the running statistics (training mode), normalises `obs`, evaluates pi and vf,
  * samples the action (or takes the mean when deterministic != 0).  Outputs (each may be NULL):

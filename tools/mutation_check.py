@@ -3,7 +3,8 @@
 a COPY of csrc/ (the fixes were commits b1ce333 and 8b54a4a, and round 6's log_plane fix), builds it, and runs the round-6 coverage
 tests against the mutant: every mutant must be caught ("What's weak" 2 / "Next round" 1).  The learner mutants
 (the PPO update, fwgym_learner.h) are plausible slips of a rewrite of its kernels; they run the emulated forms of
-tests/test_ppo_hip_contract.py.
+tests/test_ppo_hip_contract.py.  The head mutants (head_*: the rollout head, fwgym_actor.h) likewise, against the emulated forms of
+tests/test_actor_contract.py; they are built for the host emulation only.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
@@ -78,6 +79,28 @@ MUTANTS = {
     "update_config_keeps_generation": [
         ("fwgym.hip", "    dy.generation = h->hd.generation + 1u;   // ranges may have changed: prepared reset draws are stale",
          "    dy.generation = h->hd.generation;")],
+    # ---- the rollout head (fwgym_actor.h), arithmetic only and in bounds: plausible slips of a rewrite for speed; they run the
+    # emulated forms of tests/test_actor_contract.py.  One of the three split-bf16 products (A_lo B_hi) dropped: from mma3 and
+    # from the two forms of it the head's networks go through (mma3x2: layers 1 and 2, mma3s: layer 3; mma3 itself serves the learner)
+    "head_split_drops_a_lo_product": [
+        ("fwgym_actor.h", "        acc = fwg_mfma_bf16(a_lo, b_hi, acc);\n", ""),
+        ("fwgym_actor.h", "        acc0 = fwg_mfma_bf16(a0_lo, b_hi, acc0); acc1 = fwg_mfma_bf16(a1_lo, b_hi, acc1);\n", ""),
+        ("fwgym_actor.h", "        acc_a = fwg_mfma_bf16(a_lo, b_hi, acc_a);\n", "")],
+    # the observation fold without the term for the distance between the batch mean and the running mean
+    "head_fold_drops_delta_term": [
+        ("fwgym_actor.h", "const float mm = v * cnt + bvar * n_obs + s1 * s1 * (cnt * n_obs / tt);", "const float mm = v * cnt + bvar * n_obs;")],
+    # the discounted return carried over an episode end
+    "head_return_ignores_done": [
+        ("fwgym_actor.h", "        A.ret[e] = (A.done != nullptr && A.done[e]) ? 0.f : r;", "        A.ret[e] = r;")],
+    # the sampling noise drawn for env ids that start at 0 whatever env_id_base says
+    "head_noise_ignores_env_base": [
+        ("fwgym_actor.h", "philox4x32((unsigned)(A.env_base + e), act_ctr,", "philox4x32((unsigned)(e), act_ctr,")],
+    # the scalar load path (obs_dim % 4 != 0) one feature short
+    "head_scalar_load_one_short": [
+        ("fwgym_actor.h", "if (f0 + i < A.D) v[i] = A.obs[e * A.D + f0 + i];", "if (f0 + i + 1 < A.D) v[i] = A.obs[e * A.D + f0 + i];")],
+    # the act counter (the noise stream's counter, and the rotation of the accumulator sets) kept by deterministic acts
+    "head_counter_skips_deterministic_acts": [
+        ("fwgym_actor.h", "                S1.act_counter = act_ctr + 1u;", "                S1.act_counter = act_ctr + (A.deterministic ? 0u : 1u);")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -85,7 +108,8 @@ _LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_con
 # (the regime in which prepared draws are completed, and the seed change: the 45-step regime never holds a complete draw)
 _CURRICULUM_TESTS = ["-k", "sparse or another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
 # the pytest arguments each mutant runs in `emu` mode
-TESTS = {name: (_LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else
+_HEAD_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract.py")]
+TESTS = {name: (_LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
