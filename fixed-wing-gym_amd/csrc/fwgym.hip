@@ -1606,7 +1606,7 @@ __global__ void k_check_nan(const float* __restrict__ a, long n, int* flag) {
 // fwg_finish_episodes: finished-episode records not yet collected -> metrics block + success sums (per-wave reduction by
 // shuffles, one atomic per value per wave: the per-GPU part of the success reduction of examples/train_rl_controller.py:51-66,
 // 80-85); the pending mark is cleared.  One lane per env; a wave without a pending record leaves after one 16-byte load.
-__device__ __forceinline__ unsigned long long finish_wave(const DevCfg& c, const KArgs& A, long e, int lane, bool pending, float4 fl) {
+__device__ __forceinline__ void finish_wave(const DevCfg& c, const KArgs& A, long e, int lane, bool pending, float4 fl) {
     float red[FWG_N_REDUCE];
 #pragma unroll
     for (int i = 0; i < FWG_N_REDUCE; ++i) red[i] = 0.f;
@@ -1625,18 +1625,12 @@ __device__ __forceinline__ unsigned long long finish_wave(const DevCfg& c, const
 #pragma unroll
     for (int i = 0; i < 32; ++i) v32[i] = i < FWG_N_REDUCE ? red[i] : 0.f;
     const float tot = wave_totals32(v32, lane);   // lane l holds the total of value l & 31
-    unsigned long long old = 0ull;   // (returned: the caller's ticket waits for the atomics to have been performed)
-    if (lane < FWG_N_REDUCE && tot != 0.f) old = atomicAdd(A.reduce + lane, reduce_fixed(lane, tot));
-    return old;
+    if (lane < FWG_N_REDUCE && tot != 0.f) atomicAdd(A.reduce + lane, reduce_fixed(lane, tot));
 }
-// TAKE (fwg_reduce_success_device, FWGYM_TAKE=ticket): the same launch also hands the sums out and clears them -- the block that
-// finishes LAST (a device-wide ticket, A.reduce[FWG_N_REDUCE]) exchanges the 16 accumulators for zero and writes the floats.
-// Ordering without a fence: a block's accumulating atomics RETURN their old values and the ticket is taken only after they
-// have come back (performed at the device's coherence point), so the last ticket holder's exchanges see every contribution.
-// (First form of round 6: __threadfence() before the ticket -- on this part an agent-scope release writes the XCD's L2 back:
-// 21.6 us per launch under rocprofv3 against ~4.5 + ~2 for the two launches it replaced; profiles/r06_finish_take.txt.)
-template <bool TAKE>
-__global__ __launch_bounds__(FWG_WAVE) void k_finish(const DevCfg* __restrict__ cp, const KArgs A, float* __restrict__ take_out) {
+// (Handing the sums out is a launch of its own, k_reduce_take below.  Round 6 also had a one-launch form -- the block that
+// finished last, by a device-wide ticket, exchanged the accumulators for zero -- which measured the same and was removed:
+// profiles/r06_finish_take.txt.)
+__global__ __launch_bounds__(FWG_WAVE) void k_finish(const DevCfg* __restrict__ cp, const KArgs A) {
     const DevCfg& c = *cp;
     const int lane = threadIdx.x;
     const long e0 = (long)blockIdx.x * FWG_WAVE + lane;
@@ -1644,24 +1638,9 @@ __global__ __launch_bounds__(FWG_WAVE) void k_finish(const DevCfg* __restrict__ 
     const long e = valid ? e0 : A.N - 1;
     const float4 fl = CGROUP(A.S, A.N, (c.L.gym >> 2) + 1, e);
     const bool pending = valid && (f2u(fl.x) & FWG_FLAG_FIN_PENDING);
-    unsigned long long seen = 0ull;
-    if (__ballot(pending) != 0ull) seen = finish_wave(c, A, e, lane, pending, fl);
-    if (TAKE) {
-        FWG_TOUCH((unsigned)seen);   // (the returned values in registers: the wave's accumulating atomics have been performed)
-        FWG_TOUCH((unsigned)(seen >> 32));
-        unsigned ticket = 0u;
-        if (lane == 0) ticket = atomicAdd(reinterpret_cast<unsigned*>(A.reduce + FWG_N_REDUCE), 1u);
-        const bool last = __ballot(lane == 0 && ticket == gridDim.x - 1u) != 0ull;
-        if (last) {
-            if (lane < FWG_N_REDUCE) {
-                const long long q = (long long)atomicExch(A.reduce + lane, 0ull);
-                take_out[lane] = lane < 5 ? (float)q : (float)((double)q / (double)FWG_ACC_SCALE);
-            }
-            if (lane == 0) *reinterpret_cast<unsigned*>(A.reduce + FWG_N_REDUCE) = 0u;   // (the next launch is stream-ordered behind this one)
-        }
-    }
+    if (__ballot(pending) != 0ull) finish_wave(c, A, e, lane, pending, fl);
 }
-// the two-launch form of fwg_reduce_success_device (default): fixed-point sums -> floats, accumulators cleared
+// fwg_reduce_success_device, after k_finish: fixed-point sums -> floats, accumulators cleared
 __global__ void k_reduce_take(unsigned long long* __restrict__ acc, float* __restrict__ out) {
     const int i = threadIdx.x;
     if (i < FWG_N_REDUCE) {
@@ -1795,7 +1774,6 @@ struct fwg_handle {
     unsigned generation_at_capture;   // configuration generation the captured launch sequences belong to
     int spec_at_capture;              // ... and the kernel INSTANCE they hold (a frozen kernel has the configuration's values folded in)
     StepSlots* d_slots;
-    size_t lds_bytes;
     float* last_metrics_out;      // metrics block of the last fwg_step (what fwg_reduce_success* collect into)
     unsigned* d_mq;               // simulator.model / randomize_scaling: two reset queues [2][1 + N] (by the parity of the step count)
     int model_all_stale;          // every env needs a new prepared set (start, fwg_update_config, fwg_seed): full-grid draw next
@@ -2031,12 +2009,32 @@ static int lower_config(const fwg_config& c, DevCfg* d, DynCfg* dy, std::string*
 // frozen configurations compiled into this library (host copies for matching)
 #define FWG_SPEC_HOST(i) &kSpecWords##i,
 static const SpecWords* const kSpecTable[] = {FWG_SPEC_LIST(FWG_SPEC_HOST) nullptr};
+#undef FWG_SPEC_HOST
+// Which kernel instance a handle runs, as a compile-time tag: f(Instance<TURB, SPEC>()) for the frozen configuration or shape
+// instance `spec`; false (f not called) for anything else -- the generic kernels, which read TURB from the configuration.
+// The ONE place the lists of the build are expanded for dispatch: launches, the fused rollout step and match_shape come here.
+template <bool TURB_, int SPEC_> struct Instance { static constexpr bool TURB = TURB_; static constexpr int SPEC = SPEC_; };
+template <class F>
+static bool with_instance(int spec, F&& f) {
+    switch (spec) {
+#define FWG_INSTANCE_CASE(i) case i: f(Instance<(kSpec##i.turbulence != 0), i>()); return true;
+#define FWG_SHAPE_CASE(i) case FWG_SHAPE_BASE + i: f(Instance<(kSpec##i.turbulence != 0), FWG_SHAPE_BASE + i>()); return true;
+        FWG_SPEC_LIST(FWG_INSTANCE_CASE) FWG_SHAPE_LIST(FWG_SHAPE_CASE)
+#undef FWG_INSTANCE_CASE
+#undef FWG_SHAPE_CASE
+        default: return false;
+    }
+}
 static int match_shape(const DevCfg& d) {
     // a shape instance whose structure is this configuration's?  (merging d's values into the instance gives d back bit for bit)
 #ifndef FWG_EMU   /* (the host emulation reads V(c) as c: frozen and generic kernels only) */
-#define FWG_SHAPE_MATCH(i) { const DevCfg m = merge_values(kSpec##i, &d); if (memcmp(&m, &d, sizeof(DevCfg)) == 0) return FWG_SHAPE_BASE + i; }
-    FWG_SHAPE_LIST(FWG_SHAPE_MATCH)
-#undef FWG_SHAPE_MATCH
+    for (int i = 0; kSpecTable[i] != nullptr; ++i) {
+        if (!with_instance(FWG_SHAPE_BASE + i, [](auto) {})) continue;   // (not every frozen configuration is built as one)
+        DevCfg m;
+        memcpy(&m, kSpecTable[i], sizeof(DevCfg));
+        m = merge_values(m, &d);
+        if (memcmp(&m, &d, sizeof(DevCfg)) == 0) return FWG_SHAPE_BASE + i;
+    }
 #endif
     return -1;
 }
@@ -2051,8 +2049,24 @@ static int match_spec(const DevCfg& d) {
     return match_shape(d);
 }
 
+// every entry point that takes a fwg_config: the caller's struct is this build's, and it lowers -- else the error is set
+static int lower_checked(const fwg_config* cfg, DevCfg* d, DynCfg* dy) {
+    if (cfg->abi_version != FWG_ABI_VERSION || cfg->struct_bytes != sizeof(fwg_config))
+        return fail_with(FWG_ERR_ABI, "fwg_config version/size mismatch");
+    std::string why;
+    if (lower_config(*cfg, d, dy, &why) != 0) return fail_with(FWG_ERR_INVALID, why);
+    return FWG_OK;
+}
+
 template <bool IS_STEP>
 static void launch(const fwg_handle* h, const KArgs& A, hipStream_t stream);
+static dim3 wave_grid(int64_t n_envs) { return dim3((unsigned)((n_envs + FWG_WAVE - 1) / FWG_WAVE)); }   // one lane per env
+// dynamic LDS of a step / reset launch of this handle's configuration
+static size_t step_lds_bytes(const fwg_handle* h, bool generic, bool split = false) {
+    return (size_t)lds_map(h->h.obs_dim, h->h.n_obs, h->h.L.window, h->h.use_cmd_ring, generic, h->h.obs_log, split).total * sizeof(float);
+}
+// simulator.model / randomize_scaling: the reset queue the launches of step `g` append to (the next step's draw works it off)
+static unsigned* mq_queue(const fwg_handle* h, int64_t g) { return h->d_mq + (size_t)(g & 1) * (size_t)(1 + h->n_envs); }
 
 extern "C" {
 
@@ -2061,71 +2075,70 @@ const char* fwg_last_error(void) { return g_err.c_str(); }
 
 int fwg_get_layout(const fwg_config* cfg, fwg_layout* out) {
     if (!cfg || !out) return fail_with(FWG_ERR_INVALID, "null argument");
-    if (cfg->abi_version != FWG_ABI_VERSION || cfg->struct_bytes != sizeof(fwg_config))
-        return fail_with(FWG_ERR_ABI, "fwg_config version/size mismatch");
-    std::string why;
-    if (compute_layout(*cfg, out, &why) < 0) return fail_with(FWG_ERR_INVALID, why);
+    DevCfg d;
+    DynCfg dy;
+    const int rc = lower_checked(cfg, &d, &dy);
+    if (rc != FWG_OK) return rc;
+    *out = d.L;
     return FWG_OK;
 }
 
 int fwg_create(const fwg_config* cfg, int64_t n_envs, int device, void* state_arena, int64_t env_id_base, fwg_handle** out) {
     if (!cfg || !out || !state_arena || n_envs < 1) return fail_with(FWG_ERR_INVALID, "null/invalid argument");
-    if (cfg->abi_version != FWG_ABI_VERSION || cfg->struct_bytes != sizeof(fwg_config))
-        return fail_with(FWG_ERR_ABI, "fwg_config version/size mismatch");
-    fwg_handle* h = new fwg_handle();
-    h->cfg = *cfg;
-    std::string why;
-    if (lower_config(*cfg, &h->h, &h->hd, &why) != 0) { delete h; return fail_with(FWG_ERR_INVALID, why); }
-    h->spec = match_spec(h->h);
-    h->spec_at_capture = h->spec;
-    {   // FWGYM_SPLIT=0 keeps the one-wave kernel (A/B measurements)
-        const char* env = getenv("FWGYM_SPLIT");
-        h->split = !(env != nullptr && env[0] == '0');
-    }
-    h->n_envs = n_envs; h->env_base = env_id_base; h->device = device; h->seed = 0; h->gstep = 0;
-    h->arena = (float*)state_arena;
-    if ((int64_t)h->h.L.rows * n_envs >= (int64_t)1 << 30) { delete h; return fail_with(FWG_ERR_INVALID, "rows*n_envs must be < 2^30"); }
-    if (lds_map(h->h.obs_dim, h->h.n_obs, h->h.L.window, h->h.use_cmd_ring, true).total * sizeof(float) > 64 * 1024) {
-        delete h; return fail_with(FWG_ERR_INVALID, "observation too large for the LDS scratch");
-    }
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipMalloc((void**)&h->d_cfg, sizeof(DevCfg)));
-    HIP_TRY(hipMalloc((void**)&h->d_dyn, sizeof(DynCfg)));
-    HIP_TRY(hipMemcpy(h->d_dyn, &h->hd, sizeof(DynCfg), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc((void**)&h->d_reduce, sizeof(unsigned long long) * (FWG_N_REDUCE + 1)));   // (+ the ticket of k_finish<true>)
-    HIP_TRY(hipMalloc((void**)&h->d_flag, sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&h->d_slots, 2 * sizeof(StepSlots)));
-    HIP_TRY(hipMemset(h->d_slots, 0, 2 * sizeof(StepSlots)));
-    h->graph_mode = 0;
-    HIP_TRY(hipMemcpy(h->d_cfg, &h->h, sizeof(DevCfg), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->d_reduce, 0, sizeof(unsigned long long) * (FWG_N_REDUCE + 1)));
-    HIP_TRY(hipMemset(h->d_flag, 0, sizeof(int)));
-    h->d_mq = nullptr;
-    h->model_all_stale = 1;
-    if (h->h.model_n > 0 || h->h.randomize_scaling) {
-        HIP_TRY(hipMalloc((void**)&h->d_mq, 2 * (size_t)(1 + n_envs) * sizeof(unsigned)));
-        HIP_TRY(hipMemset(h->d_mq, 0, 2 * (size_t)(1 + n_envs) * sizeof(unsigned)));
-    }
+    fwg_handle* h = new fwg_handle();   // (every member zero / null)
+    h->device = device;
+    const int rc = [&]() -> int {
+        const int lowered = lower_checked(cfg, &h->h, &h->hd);
+        if (lowered != FWG_OK) return lowered;
+        h->cfg = *cfg;
+        h->spec = match_spec(h->h);
+        h->spec_at_capture = h->spec;
+        {   // FWGYM_SPLIT=0 keeps the one-wave kernel (A/B measurements)
+            const char* env = getenv("FWGYM_SPLIT");
+            h->split = !(env != nullptr && env[0] == '0');
+        }
+        h->n_envs = n_envs; h->env_base = env_id_base;
+        h->arena = (float*)state_arena;
+        h->model_all_stale = 1;
+        if ((int64_t)h->h.L.rows * n_envs >= (int64_t)1 << 30) return fail_with(FWG_ERR_INVALID, "rows*n_envs must be < 2^30");
+        if (lds_map(h->h.obs_dim, h->h.n_obs, h->h.L.window, h->h.use_cmd_ring, true).total * sizeof(float) > 64 * 1024)
+            return fail_with(FWG_ERR_INVALID, "observation too large for the LDS scratch");
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMalloc((void**)&h->d_cfg, sizeof(DevCfg)));
+        HIP_TRY(hipMalloc((void**)&h->d_dyn, sizeof(DynCfg)));
+        HIP_TRY(hipMemcpy(h->d_dyn, &h->hd, sizeof(DynCfg), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc((void**)&h->d_reduce, sizeof(unsigned long long) * FWG_N_REDUCE));
+        HIP_TRY(hipMalloc((void**)&h->d_flag, sizeof(int)));
+        HIP_TRY(hipMalloc((void**)&h->d_slots, 2 * sizeof(StepSlots)));
+        HIP_TRY(hipMemset(h->d_slots, 0, 2 * sizeof(StepSlots)));
+        HIP_TRY(hipMemcpy(h->d_cfg, &h->h, sizeof(DevCfg), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(h->d_reduce, 0, sizeof(unsigned long long) * FWG_N_REDUCE));
+        HIP_TRY(hipMemset(h->d_flag, 0, sizeof(int)));
+        if (h->h.model_n > 0 || h->h.randomize_scaling) {
+            HIP_TRY(hipMalloc((void**)&h->d_mq, 2 * (size_t)(1 + n_envs) * sizeof(unsigned)));
+            HIP_TRY(hipMemset(h->d_mq, 0, 2 * (size_t)(1 + n_envs) * sizeof(unsigned)));
+        }
+        return FWG_OK;
+    }();
+    if (rc != FWG_OK) { fwg_destroy(h); return rc; }
     *out = h;
     return FWG_OK;
 }
 
-int fwg_destroy(fwg_handle* h) {
+int fwg_destroy(fwg_handle* h) {   // (also the failure exit of fwg_create: any of the buffers may still be null)
     if (!h) return FWG_OK;
     (void)hipSetDevice(h->device);
-    (void)hipFree(h->d_cfg); (void)hipFree(h->d_dyn); (void)hipFree(h->d_reduce); (void)hipFree(h->d_flag); (void)hipFree(h->d_slots); if (h->d_mq) (void)hipFree(h->d_mq);
+    (void)hipFree(h->d_cfg); (void)hipFree(h->d_dyn); (void)hipFree(h->d_reduce); (void)hipFree(h->d_flag); (void)hipFree(h->d_slots); (void)hipFree(h->d_mq);
     delete h;
     return FWG_OK;
 }
 
 int fwg_update_config(fwg_handle* h, const fwg_config* cfg) {
     if (!h || !cfg) return fail_with(FWG_ERR_INVALID, "null argument");
-    if (cfg->abi_version != FWG_ABI_VERSION || cfg->struct_bytes != sizeof(fwg_config))
-        return fail_with(FWG_ERR_ABI, "fwg_config version/size mismatch");
     DevCfg d;
     DynCfg dy;
-    std::string why;
-    if (lower_config(*cfg, &d, &dy, &why) != 0) return fail_with(FWG_ERR_INVALID, why);
+    const int rc = lower_checked(cfg, &d, &dy);
+    if (rc != FWG_OK) return rc;
     if (memcmp(&d.L, &h->h.L, sizeof(fwg_layout)) != 0 || d.obs_dim != h->h.obs_dim)
         return fail_with(FWG_ERR_INVALID, "fwg_update_config must not change the state layout");
     dy.generation = h->hd.generation + 1u;   // ranges may have changed: prepared reset draws are stale
@@ -2169,20 +2182,37 @@ static void base_args(const fwg_handle* h, KArgs* A) {
     A->seed_lo = (unsigned)(h->seed & 0xFFFFFFFFull); A->seed_hi = (unsigned)(h->seed >> 32);
 }
 
-static void observer_args(fwg_handle* h, KArgs* A);   // defined with the rollout head below
-static int launch_rollout(fwg_handle* h, fwg_actor* a, const KArgs& A, const ActorArgs& AA, hipStream_t stream, bool probe, bool grant = false);
+static void observer_args(const fwg_handle* h, KArgs* A);   // defined with the rollout head below
+// The KArgs of the env step at the handle's current count (fwg_step, fwg_rollout_step): outputs, ring positions (on the device
+// in graph mode), the attached head's accumulators, the reset queue.  actions == nullptr: they come from the head phase (LDS)
+static KArgs step_args(fwg_handle* h, const float* actions, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* term_code_out,
+                       float* terminal_obs_out, float* metrics_out, float* target_out) {
+    KArgs A;
+    base_args(h, &A);
+    A.actions = actions; A.obs = obs_out; A.rew = reward_out; A.done = done_out; A.term = term_code_out;
+    A.term_obs = terminal_obs_out; A.metrics = metrics_out; A.tgt_out = target_out;
+    h->last_metrics_out = metrics_out;
+    fill_slots(h, h->gstep, &A);
+    if (h->graph_mode) { A.slots_in = h->d_slots + (h->gstep & 1); A.slots_out = h->d_slots + ((h->gstep + 1) & 1); }
+    observer_args(h, &A);
+    if (h->d_mq != nullptr) A.mq = mq_queue(h, h->gstep);
+#ifdef FWG_TIMELINE
+    A.trace = h->trace;
+#endif
+    return A;
+}
 // simulator.model: before any launch that may reset an env, every env has the parameter set of its next episode prepared
 static void launch_model_draw(fwg_handle* h, const KArgs& A, hipStream_t stream, bool all) {
     if (h->h.model_n <= 0 && !h->h.randomize_scaling) return;
     if (all || h->model_all_stale) {
-        hipLaunchKernelGGL(k_model_draw, dim3((unsigned)((h->n_envs + FWG_WAVE - 1) / FWG_WAVE)), dim3(FWG_WAVE), FWG_N_PARAMS * FWG_WAVE * sizeof(float), stream, h->d_cfg, h->d_dyn, A);
+        hipLaunchKernelGGL(k_model_draw, wave_grid(h->n_envs), dim3(FWG_WAVE), FWG_N_PARAMS * FWG_WAVE * sizeof(float), stream, h->d_cfg, h->d_dyn, A);
         // (the queues hold nothing this draw has not covered; the one the coming kernel appends to starts empty)
-        (void)hipMemsetAsync(h->d_mq, 0, sizeof(unsigned), stream);
-        (void)hipMemsetAsync(h->d_mq + (size_t)(1 + h->n_envs), 0, sizeof(unsigned), stream);
+        (void)hipMemsetAsync(mq_queue(h, 0), 0, sizeof(unsigned), stream);
+        (void)hipMemsetAsync(mq_queue(h, 1), 0, sizeof(unsigned), stream);
         h->model_all_stale = 0;
     } else {   // the envs reset by the previous launch (queue of the other parity)
         hipLaunchKernelGGL(k_model_draw_q, dim3(FWG_MQ_BLOCKS), dim3(64 * FWG_MQ_WAVES), FWG_MQ_WAVES * (FWG_N_PARAMS + 4 * FWG_AERO_GROUPS) * sizeof(float), stream, h->d_cfg, h->d_dyn, A,
-                           h->d_mq + (size_t)((h->gstep - 1) & 1) * (size_t)(1 + h->n_envs), h->d_mq + (size_t)(h->gstep & 1) * (size_t)(1 + h->n_envs));
+                           mq_queue(h, h->gstep - 1), mq_queue(h, h->gstep));
     }
 }
 
@@ -2193,7 +2223,7 @@ int fwg_reset(fwg_handle* h, const uint8_t* mask, const float* init_state, const
     A.mask = mask; A.init_state = init_state; A.init_target = init_target; A.obs = obs_out;
     fill_slots(h, h->gstep - 1, &A);  // initial records take the ring position of the last completed step
     if (h->graph_mode) { A.slots_in = h->d_slots + (h->gstep & 1); A.reset_launch = 1; }
-    if (h->d_mq != nullptr) A.mq = h->d_mq + (size_t)((h->gstep - 1) & 1) * (size_t)(1 + h->n_envs);   // as if part of the last step
+    if (h->d_mq != nullptr) A.mq = mq_queue(h, h->gstep - 1);   // as if part of the last step
     launch_model_draw(h, A, (hipStream_t)stream, true);
     launch<false>(h, A, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
@@ -2203,19 +2233,8 @@ int fwg_reset(fwg_handle* h, const uint8_t* mask, const float* init_state, const
 int fwg_step(fwg_handle* h, const float* actions, float* obs_out, float* reward_out, uint8_t* done_out, uint8_t* term_code_out,
              float* terminal_obs_out, float* metrics_out, float* target_out, void* stream) {
     if (!h || !actions || !obs_out || !reward_out || !done_out || !term_code_out) return fail_with(FWG_ERR_INVALID, "null argument");
-    KArgs A;
-    base_args(h, &A);
-    A.actions = actions; A.obs = obs_out; A.rew = reward_out; A.done = done_out; A.term = term_code_out;
-    A.term_obs = terminal_obs_out; A.metrics = metrics_out; A.tgt_out = target_out;
-    h->last_metrics_out = metrics_out;
-    fill_slots(h, h->gstep, &A);
-    if (h->graph_mode) { A.slots_in = h->d_slots + (h->gstep & 1); A.slots_out = h->d_slots + ((h->gstep + 1) & 1); }
-    observer_args(h, &A);
-#ifdef FWG_TIMELINE
-    A.trace = h->trace;
-#endif
-    launch_model_draw(h, A, (hipStream_t)stream, false);
-    if (h->d_mq != nullptr) A.mq = h->d_mq + (size_t)(h->gstep & 1) * (size_t)(1 + h->n_envs);
+    const KArgs A = step_args(h, actions, obs_out, reward_out, done_out, term_code_out, terminal_obs_out, metrics_out, target_out);
+    launch_model_draw(h, A, (hipStream_t)stream, false);   // (the draw kernels take their queues as arguments of their own)
     launch<true>(h, A, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     h->gstep += 1;
@@ -2281,7 +2300,7 @@ static void launch_finish(fwg_handle* h, float* metrics_out, hipStream_t stream)
     KArgs A;
     base_args(h, &A);
     A.metrics = metrics_out;
-    hipLaunchKernelGGL(k_finish<false>, dim3((unsigned)((h->n_envs + FWG_WAVE - 1) / FWG_WAVE)), dim3(FWG_WAVE), 0, stream, h->d_cfg, A, (float*)nullptr);
+    hipLaunchKernelGGL(k_finish, wave_grid(h->n_envs), dim3(FWG_WAVE), 0, stream, h->d_cfg, A);
 }
 int fwg_finish_episodes(fwg_handle* h, float* metrics_out, void* stream) {
     if (!h) return fail_with(FWG_ERR_INVALID, "null handle");
@@ -2306,19 +2325,9 @@ int fwg_reduce_success(fwg_handle* h, float* out_host, void* stream) {
 
 int fwg_reduce_success_device(fwg_handle* h, float* out_dev, void* stream) {
     if (!h || !out_dev) return fail_with(FWG_ERR_INVALID, "null argument");
-    // default: collection, then a one-wave launch that hands the sums out and clears them.  FWGYM_TAKE=ticket: ONE launch
-    // (k_finish<true>: the block that finishes last does it) -- see k_finish for what each costs
-    static const bool ticket = [] { const char* e = getenv("FWGYM_TAKE"); return e != nullptr && e[0] == 't'; }();
-    if (ticket) {
-        KArgs A;
-        base_args(h, &A);
-        A.metrics = h->h.metrics ? h->last_metrics_out : nullptr;
-        hipLaunchKernelGGL(k_finish<true>, dim3((unsigned)((h->n_envs + FWG_WAVE - 1) / FWG_WAVE)), dim3(FWG_WAVE), 0, (hipStream_t)stream,
-                           h->d_cfg, A, out_dev);
-    } else {
-        launch_finish(h, h->last_metrics_out, (hipStream_t)stream);
-        hipLaunchKernelGGL(k_reduce_take, dim3(1), dim3(FWG_WAVE), 0, (hipStream_t)stream, h->d_reduce, out_dev);
-    }
+    // collection, then a one-wave launch that hands the sums out and clears them
+    launch_finish(h, h->last_metrics_out, (hipStream_t)stream);
+    hipLaunchKernelGGL(k_reduce_take, dim3(1), dim3(FWG_WAVE), 0, (hipStream_t)stream, h->d_reduce, out_dev);
     HIP_TRY(hipGetLastError());
     return FWG_OK;
 }
@@ -2397,24 +2406,20 @@ int fwg_num_specs(void) {
 
 int fwg_config_instance(const fwg_config* cfg) {
     if (!cfg) return fail_with(FWG_ERR_INVALID, "null argument");
-    if (cfg->abi_version != FWG_ABI_VERSION || cfg->struct_bytes != sizeof(fwg_config))
-        return fail_with(FWG_ERR_ABI, "fwg_config version/size mismatch");
     DevCfg d;
     DynCfg dy;
-    std::string why;
-    if (lower_config(*cfg, &d, &dy, &why) != 0) return fail_with(FWG_ERR_INVALID, why);
+    const int rc = lower_checked(cfg, &d, &dy);
+    if (rc != FWG_OK) return rc;
     const int i = match_spec(d);
     return i < 0 ? FWG_INSTANCE_GENERIC : i;
 }
 
 int fwg_dump_spec(const fwg_config* cfg, uint32_t* words_out, int64_t capacity) {
     if (!cfg || !words_out) return fail_with(FWG_ERR_INVALID, "null argument");
-    if (cfg->abi_version != FWG_ABI_VERSION || cfg->struct_bytes != sizeof(fwg_config))
-        return fail_with(FWG_ERR_ABI, "fwg_config version/size mismatch");
     DevCfg d;
     DynCfg dy;
-    std::string why;
-    if (lower_config(*cfg, &d, &dy, &why) != 0) return fail_with(FWG_ERR_INVALID, why);
+    const int rc = lower_checked(cfg, &d, &dy);
+    if (rc != FWG_OK) return rc;
     const int64_t n = (int64_t)(sizeof(DevCfg) / 4);
     if (capacity < n) return fail_with(FWG_ERR_INVALID, "fwg_dump_spec: buffer too small");
     memcpy(words_out, &d, sizeof(DevCfg));
@@ -2425,33 +2430,21 @@ int fwg_dump_spec(const fwg_config* cfg, uint32_t* words_out, int64_t capacity) 
 
 template <bool IS_STEP, bool TURB, int SPEC>
 static void launch_one(const fwg_handle* h, const KArgs& A, hipStream_t stream) {
-    const dim3 grid((unsigned)((h->n_envs + FWG_WAVE - 1) / FWG_WAVE)), block(FWG_WAVE);
-    const size_t lds_bytes = (size_t)lds_map(h->h.obs_dim, h->h.n_obs, h->h.L.window, h->h.use_cmd_ring, SPEC < 0, h->h.obs_log).total * sizeof(float);
+    const dim3 grid = wave_grid(h->n_envs), block(FWG_WAVE);
     if (IS_STEP) {
-#ifndef FWG_NO_SPLIT
         if (SPEC >= 0 && (h->split || SPEC >= FWG_SHAPE_BASE)) {   // (shape instances exist as the two-wave kernel only)
-            const size_t lds2 = (size_t)lds_map(h->h.obs_dim, h->h.n_obs, h->h.L.window, h->h.use_cmd_ring, false, h->h.obs_log, true).total * sizeof(float);
-            hipLaunchKernelGGL((k_step2<TURB, (SPEC >= 0 ? SPEC : 0)>), grid, dim3(2 * FWG_WAVE), lds2, stream, h->d_cfg, h->d_dyn, A);
+            hipLaunchKernelGGL((k_step2<TURB, (SPEC >= 0 ? SPEC : 0)>), grid, dim3(2 * FWG_WAVE), step_lds_bytes(h, false, true), stream, h->d_cfg, h->d_dyn, A);
             return;
         }
-#endif
 #ifndef FWG_DEV_FAST_BUILD   /* tools/isa.py -DFWG_DEV_FAST_BUILD: only the two-wave / fused kernels of the frozen configuration */
-        if constexpr (SPEC < FWG_SHAPE_BASE) hipLaunchKernelGGL((k_step<TURB, SPEC>), grid, block, lds_bytes, stream, h->d_cfg, h->d_dyn, A);
+        if constexpr (SPEC < FWG_SHAPE_BASE) hipLaunchKernelGGL((k_step<TURB, SPEC>), grid, block, step_lds_bytes(h, SPEC < 0), stream, h->d_cfg, h->d_dyn, A);
 #endif
-    } else hipLaunchKernelGGL((k_reset<TURB, SPEC>), grid, block, lds_bytes, stream, h->d_cfg, h->d_dyn, A);
+    } else hipLaunchKernelGGL((k_reset<TURB, SPEC>), grid, block, step_lds_bytes(h, SPEC < 0), stream, h->d_cfg, h->d_dyn, A);
 }
 
 template <bool IS_STEP>
 static void launch(const fwg_handle* h, const KArgs& A, hipStream_t stream) {
-    switch (h->spec) {
-#define FWG_SPEC_CASE(i) \
-    case i: launch_one<IS_STEP, (kSpec##i.turbulence != 0), i>(h, A, stream); return;
-        FWG_SPEC_LIST(FWG_SPEC_CASE)
-#define FWG_SHAPE_CASE(i) \
-    case FWG_SHAPE_BASE + i: launch_one<IS_STEP, (kSpec##i.turbulence != 0), FWG_SHAPE_BASE + i>(h, A, stream); return;
-        FWG_SHAPE_LIST(FWG_SHAPE_CASE)
-        default: break;
-    }
+    if (with_instance(h->spec, [&](auto inst) { launch_one<IS_STEP, decltype(inst)::TURB, decltype(inst)::SPEC>(h, A, stream); })) return;
 #ifndef FWG_DEV_FAST_BUILD
     if (h->h.turbulence) launch_one<IS_STEP, true, -1>(h, A, stream);
     else launch_one<IS_STEP, false, -1>(h, A, stream);
@@ -2510,8 +2503,28 @@ static ActorArgs actor_args(const fwg_actor* a) {
     return A;
 }
 
-static void observer_args(fwg_handle* h, KArgs* A) {
-    fwg_actor* a = h->observer;
+// ... of an act (fwg_actor_act, fwg_rollout_step): what the head reads and where its outputs go
+static ActorArgs act_args(const fwg_actor* a, const float* obs, const float* reward, const uint8_t* done, float* norm_obs_out, float* action_out,
+                          float* value_out, float* logp_out, float* norm_reward_out, uint8_t* done_out, int deterministic) {
+    ActorArgs A = actor_args(a);
+    A.obs = obs; A.rew = reward; A.done = done;
+    A.norm_obs = norm_obs_out; A.action = action_out; A.value = value_out; A.logp = logp_out; A.norm_rew = norm_reward_out;
+    A.done_out = done_out; A.deterministic = deterministic ? 1 : 0;
+    return A;
+}
+// the MLP head's kernel for (precise: three split-bf16 products, else one; nk1 in 1..4 chunks of 16 observation entries)
+typedef void (*actor_kernel_t)(ActorArgs);
+static actor_kernel_t actor_kernel(int precise, int nk1) {
+    static const actor_kernel_t table[2][4] = {{k_actor_act<1, 1>, k_actor_act<1, 2>, k_actor_act<1, 3>, k_actor_act<1, 4>},
+                                               {k_actor_act<3, 1>, k_actor_act<3, 2>, k_actor_act<3, 3>, k_actor_act<3, 4>}};
+    return table[precise ? 1 : 0][nk1 - 1];
+}
+
+static bool rollout_fits(const fwg_handle* h);
+static bool rollout_grant_lds(const fwg_handle* h);
+
+static void observer_args(const fwg_handle* h, KArgs* A) {
+    const fwg_actor* a = h->observer;
     if (!a) return;
     A->acc = a->d_acc;   // three sets; the step adds into set (act counter of the current statistics copy) % 3
     A->acc_ctr = &a->d_stats[a->parity].act_counter;
@@ -2530,8 +2543,7 @@ int fwg_attach_observer(fwg_handle* h, fwg_actor* a) {
     h->observer = a;
     // the one-launch rollout step's dynamic LDS (both head variants), asked for here and now: attach is never captured
     h->rollout_lds_granted = 0;
-    if (a && h->spec >= 0 && h->split && launch_rollout(h, a, KArgs(), ActorArgs(), nullptr, true) == 0)
-        h->rollout_lds_granted = launch_rollout(h, a, KArgs(), ActorArgs(), nullptr, false, true) == 0 ? 1 : 0;
+    if (a && h->spec >= 0 && h->split && rollout_fits(h)) h->rollout_lds_granted = rollout_grant_lds(h) ? 1 : 0;
     return FWG_OK;
 }
 
@@ -2563,41 +2575,41 @@ int fwg_actor_create(int device, int64_t n_envs, int obs_dim, int act_dim, float
     a->device = device; a->n_envs = n_envs; a->D = obs_dim; a->act_dim = act_dim; a->nk1 = (obs_dim + 15) / 16;
     a->gamma = gamma; a->clip_obs = clip_obs; a->clip_rew = clip_reward; a->eps = epsilon;
     a->training = 1; a->precise = 1;
-    const size_t nfrag = (size_t)2 * 2 * actor_frags(a->nk1) * 64;
-    HIP_TRY(hipMalloc((void**)&a->d_stats, 2 * sizeof(ActorStats)));
     a->acc_cols = acc_cols_for(obs_dim);
-    const size_t acc_bytes = (size_t)FWG_ACC_SETS * FWG_ACC_SHARDS * a->acc_cols * sizeof(unsigned long long);
-    HIP_TRY(hipMalloc((void**)&a->d_acc, acc_bytes));
-    HIP_TRY(hipMemset(a->d_acc, 0, acc_bytes));
-    HIP_TRY(hipMalloc((void**)&a->d_frags, nfrag * sizeof(frag_t)));
-    HIP_TRY(hipMalloc((void**)&a->d_bias, (2 * FWG_ACT_BIAS_FLOATS + FWG_CNN_PARAMS) * sizeof(float)));   // (+ the conv, behind)
-    HIP_TRY(hipMemset(a->d_bias, 0, (2 * FWG_ACT_BIAS_FLOATS + FWG_CNN_PARAMS) * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&a->d_log_std, FWG_ACT_MAX_ACT * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&a->d_ret, (size_t)n_envs * sizeof(float)));
-    HIP_TRY(hipMemset(a->d_frags, 0, nfrag * sizeof(frag_t)));
-    HIP_TRY(hipMemset(a->d_log_std, 0, FWG_ACT_MAX_ACT * sizeof(float)));
-    HIP_TRY(hipMemset(a->d_ret, 0, (size_t)n_envs * sizeof(float)));
-    ActorStats s[2];
-    memset(s, 0, sizeof(s));
-    for (int p = 0; p < 2; ++p) {   // RunningMeanStd(epsilon=1e-4): mean 0, var 1, count 1e-4
-        for (int f = 0; f < FWG_ACT_MAX_OBS; ++f) s[p].var[f] = 1.f;
-        s[p].count = 1e-4f; s[p].ret_var = 1.f; s[p].ret_count = 1e-4f;
-    }
-    HIP_TRY(hipMemcpy(a->d_stats, s, sizeof(s), hipMemcpyHostToDevice));
     a->lds_act[0] = actor_lds_bytes(a->nk1, 1);
     a->lds_act[1] = actor_lds_bytes(a->nk1, 2);
-    // more than 64 KiB of dynamic LDS per workgroup has to be asked for (gfx950: 160 KiB per CU)
-    {
-        const void* k1[4] = {(const void*)k_actor_act<1, 1>, (const void*)k_actor_act<1, 2>, (const void*)k_actor_act<1, 3>, (const void*)k_actor_act<1, 4>};
-        const void* k3[4] = {(const void*)k_actor_act<3, 1>, (const void*)k_actor_act<3, 2>, (const void*)k_actor_act<3, 3>, (const void*)k_actor_act<3, 4>};
-        HIP_TRY(hipFuncSetAttribute(k1[a->nk1 - 1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->lds_act[0]));
-        HIP_TRY(hipFuncSetAttribute(k3[a->nk1 - 1], hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->lds_act[1]));
-    }
+    const int rc = [&]() -> int {
+        const size_t nfrag = (size_t)2 * 2 * actor_frags(a->nk1) * 64;
+        HIP_TRY(hipMalloc((void**)&a->d_stats, 2 * sizeof(ActorStats)));
+        const size_t acc_bytes = (size_t)FWG_ACC_SETS * FWG_ACC_SHARDS * a->acc_cols * sizeof(unsigned long long);
+        HIP_TRY(hipMalloc((void**)&a->d_acc, acc_bytes));
+        HIP_TRY(hipMemset(a->d_acc, 0, acc_bytes));
+        HIP_TRY(hipMalloc((void**)&a->d_frags, nfrag * sizeof(frag_t)));
+        HIP_TRY(hipMalloc((void**)&a->d_bias, (2 * FWG_ACT_BIAS_FLOATS + FWG_CNN_PARAMS) * sizeof(float)));   // (+ the conv, behind)
+        HIP_TRY(hipMemset(a->d_bias, 0, (2 * FWG_ACT_BIAS_FLOATS + FWG_CNN_PARAMS) * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&a->d_log_std, FWG_ACT_MAX_ACT * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&a->d_ret, (size_t)n_envs * sizeof(float)));
+        HIP_TRY(hipMemset(a->d_frags, 0, nfrag * sizeof(frag_t)));
+        HIP_TRY(hipMemset(a->d_log_std, 0, FWG_ACT_MAX_ACT * sizeof(float)));
+        HIP_TRY(hipMemset(a->d_ret, 0, (size_t)n_envs * sizeof(float)));
+        ActorStats s[2];
+        memset(s, 0, sizeof(s));
+        for (int p = 0; p < 2; ++p) {   // RunningMeanStd(epsilon=1e-4): mean 0, var 1, count 1e-4
+            for (int f = 0; f < FWG_ACT_MAX_OBS; ++f) s[p].var[f] = 1.f;
+            s[p].count = 1e-4f; s[p].ret_var = 1.f; s[p].ret_count = 1e-4f;
+        }
+        HIP_TRY(hipMemcpy(a->d_stats, s, sizeof(s), hipMemcpyHostToDevice));
+        // more than 64 KiB of dynamic LDS per workgroup has to be asked for (gfx950: 160 KiB per CU)
+        for (int precise = 0; precise < 2; ++precise)
+            HIP_TRY(hipFuncSetAttribute((const void*)actor_kernel(precise, a->nk1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a->lds_act[precise]));
+        return FWG_OK;
+    }();
+    if (rc != FWG_OK) { fwg_actor_destroy(a); return rc; }
     *out = a;
     return FWG_OK;
 }
 
-void fwg_actor_destroy(fwg_actor* a) {
+void fwg_actor_destroy(fwg_actor* a) {   // (also the failure exit of fwg_actor_create: any of the buffers may still be null)
     if (!a) return;
     (void)hipFree(a->d_stats); (void)hipFree(a->d_acc); (void)hipFree(a->d_frags); (void)hipFree(a->d_bias); (void)hipFree(a->d_log_std); (void)hipFree(a->d_ret);
     delete a;
@@ -2722,68 +2734,57 @@ int fwg_actor_act(fwg_actor* a, const float* obs, const float* reward, const uin
                   int deterministic, void* stream) {
     if (!a || !obs) return fail_with(FWG_ERR_INVALID, "fwg_actor_act: null argument");
     HIP_TRY(hipSetDevice(a->device));
-    ActorArgs A = actor_args(a);
-    A.obs = obs; A.rew = reward; A.done = done;
-    A.norm_obs = norm_obs_out; A.action = action_out; A.value = value_out; A.logp = logp_out; A.norm_rew = norm_reward_out;
-    A.done_out = done_out; A.deterministic = deterministic ? 1 : 0;
+    const ActorArgs A = act_args(a, obs, reward, done, norm_obs_out, action_out, value_out, logp_out, norm_reward_out, done_out, deterministic);
     const dim3 grid((unsigned)((a->n_envs + FWG_ACT_ENVS - 1) / FWG_ACT_ENVS)), block(64 * FWG_ACT_WAVES);
     hipStream_t st = (hipStream_t)stream;
     if (a->cnn_filters) {
         if (a->precise) hipLaunchKernelGGL((k_actor_act_cnn<3>), grid, block, a->lds_cnn[1], st, A);
         else hipLaunchKernelGGL((k_actor_act_cnn<1>), grid, block, a->lds_cnn[0], st, A);
-        HIP_TRY(hipGetLastError());
-        a->parity ^= 1;
-        return FWG_OK;
-    }
-#define FWG_ACT_LAUNCH(NK)                                                                                \
-    case NK:                                                                                              \
-        if (a->precise) hipLaunchKernelGGL((k_actor_act<3, NK>), grid, block, a->lds_act[1], st, A);     \
-        else hipLaunchKernelGGL((k_actor_act<1, NK>), grid, block, a->lds_act[0], st, A);                \
-        break;
-    switch (a->nk1) { FWG_ACT_LAUNCH(1) FWG_ACT_LAUNCH(2) FWG_ACT_LAUNCH(3) FWG_ACT_LAUNCH(4) default: break; }
-#undef FWG_ACT_LAUNCH
+    } else hipLaunchKernelGGL(actor_kernel(a->precise, a->nk1), grid, block, a->lds_act[a->precise], st, A);
     HIP_TRY(hipGetLastError());
     a->parity ^= 1;
     return FWG_OK;
 }
 
 }  // extern "C"
-// ---- the head and the env step in one launch
-// grant = true (fwg_attach_observer, never inside a stream capture): asks for the dynamic LDS of BOTH head variants -- more than
-// 64 KiB per workgroup has to be requested per kernel; done eagerly and recorded in the handle, so that no launch (possibly the
-// first one of a variant inside a capture, after fwg_actor_configure) ever has to
-template <bool TURB, int SPEC>
-static int launch_rollout_one(fwg_handle* h, fwg_actor* a, const KArgs& A, const ActorArgs& AA, hipStream_t stream, bool grant) {
-    if constexpr (SPEC >= 0) {
-        if constexpr (SpecCfg<SPEC>::rollout_ok) {
-            if (grant) {
-                const size_t b3 = (size_t)rollout_lds_floats(h->h, 3) * sizeof(float), b1 = (size_t)rollout_lds_floats(h->h, 1) * sizeof(float);
-                if (b3 > 160 * 1024 || b1 > 160 * 1024) return 1;
-                if (hipFuncSetAttribute((const void*)k_rollout<TURB, SPEC, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b3) != hipSuccess) return 1;
-                if (hipFuncSetAttribute((const void*)k_rollout<TURB, SPEC, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b1) != hipSuccess) return 1;
-                return 0;
-            }
-            const int hsplit = a->precise ? 3 : 1;
-            const size_t bytes = (size_t)rollout_lds_floats(h->h, hsplit) * sizeof(float);
-            if (bytes > 160 * 1024 || !h->rollout_lds_granted) return 1;
-            const dim3 grid((unsigned)((h->n_envs + FWG_RO_ENVS - 1) / FWG_RO_ENVS)), block(2 * FWG_RO_ENVS);
-            if (a->precise) hipLaunchKernelGGL((k_rollout<TURB, SPEC, 3>), grid, block, bytes, stream, h->d_cfg, h->d_dyn, A, AA);
-            else hipLaunchKernelGGL((k_rollout<TURB, SPEC, 1>), grid, block, bytes, stream, h->d_cfg, h->d_dyn, A, AA);
-            return 0;
-        }
-    }
-    return 1;
+// ---- the head and the env step in one launch (k_rollout: frozen configurations with SpecCfg<SPEC>::rollout_ok), by job
+static size_t rollout_lds_bytes(const fwg_handle* h, int hsplit) { return (size_t)rollout_lds_floats(h->h, hsplit) * sizeof(float); }
+// does the handle's instance have the fused kernel, within the CU's LDS?  (a frozen instance's h->h IS its frozen configuration)
+static bool rollout_fits(const fwg_handle* h) {
+    bool ok = false;
+    with_instance(h->spec, [&](auto inst) { ok = SpecCfg<decltype(inst)::SPEC>::rollout_ok && rollout_lds_bytes(h, 3) <= 160 * 1024; });
+    return ok;
 }
-static int launch_rollout(fwg_handle* h, fwg_actor* a, const KArgs& A, const ActorArgs& AA, hipStream_t stream, bool probe, bool grant) {
-    switch (h->spec) {
-#define FWG_SPEC_RO(i) \
-    case i: if (probe) return (SpecCfg<i>::rollout_ok && (size_t)rollout_lds_floats(kSpec##i, 3) * sizeof(float) <= 160 * 1024) ? 0 : 1; \
-            return launch_rollout_one<(kSpec##i.turbulence != 0), i>(h, a, A, AA, stream, grant);
-        FWG_SPEC_LIST(FWG_SPEC_RO)
-#undef FWG_SPEC_RO
-        default: break;
-    }
-    return 1;
+// fwg_attach_observer (never inside a stream capture): asks for the dynamic LDS of BOTH head variants -- more than 64 KiB per
+// workgroup has to be requested per kernel; done eagerly and recorded in the handle, so that no launch (possibly the first one
+// of a variant inside a capture, after fwg_actor_configure) ever has to
+static bool rollout_grant_lds(const fwg_handle* h) {
+    bool ok = false;
+    with_instance(h->spec, [&](auto inst) {
+        using I = decltype(inst);
+        if constexpr (SpecCfg<I::SPEC>::rollout_ok) {
+            const size_t b3 = rollout_lds_bytes(h, 3), b1 = rollout_lds_bytes(h, 1);
+            ok = b3 <= 160 * 1024 && b1 <= 160 * 1024 &&
+                 hipFuncSetAttribute((const void*)k_rollout<I::TURB, I::SPEC, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b3) == hipSuccess &&
+                 hipFuncSetAttribute((const void*)k_rollout<I::TURB, I::SPEC, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b1) == hipSuccess;
+        }
+    });
+    return ok;
+}
+static bool launch_rollout(const fwg_handle* h, const fwg_actor* a, const KArgs& A, const ActorArgs& AA, hipStream_t stream) {
+    bool ok = false;
+    with_instance(h->spec, [&](auto inst) {
+        using I = decltype(inst);
+        if constexpr (SpecCfg<I::SPEC>::rollout_ok) {
+            const size_t bytes = rollout_lds_bytes(h, a->precise ? 3 : 1);
+            if (bytes > 160 * 1024 || !h->rollout_lds_granted) return;
+            const dim3 grid((unsigned)((h->n_envs + FWG_RO_ENVS - 1) / FWG_RO_ENVS)), block(2 * FWG_RO_ENVS);
+            if (a->precise) hipLaunchKernelGGL((k_rollout<I::TURB, I::SPEC, 3>), grid, block, bytes, stream, h->d_cfg, h->d_dyn, A, AA);
+            else hipLaunchKernelGGL((k_rollout<I::TURB, I::SPEC, 1>), grid, block, bytes, stream, h->d_cfg, h->d_dyn, A, AA);
+            ok = true;
+        }
+    });
+    return ok;
 }
 
 extern "C" {
@@ -2793,7 +2794,7 @@ int fwg_rollout_available(const fwg_handle* h, const fwg_actor* a) {
     if (h->h.model_n > 0 || h->h.randomize_scaling) return 0;   // (the per-env parameter queue launch sits between head and step)
     if (a->act_dim != 3 || a->log_env != nullptr || a->cnn_filters) return 0;   // (k_rollout runs the MLP head only)
     if (!h->rollout_lds_granted) return 0;
-    return launch_rollout(const_cast<fwg_handle*>(h), const_cast<fwg_actor*>(a), KArgs(), ActorArgs(), nullptr, true) == 0 ? 1 : 0;
+    return rollout_fits(h) ? 1 : 0;
 }
 
 int fwg_rollout_step(fwg_handle* h, fwg_actor* a, float* norm_obs_out, float* action_out, float* value_out, float* logp_out,
@@ -2805,24 +2806,12 @@ int fwg_rollout_step(fwg_handle* h, fwg_actor* a, float* norm_obs_out, float* ac
                                           "and this head attached (fwg_attach_observer); use fwg_step + fwg_actor_act otherwise");
     HIP_TRY(hipSetDevice(a->device));
     // head: on the observation / reward / done flags the env's last step left in obs_io / reward_io / done_io
-    ActorArgs AA = actor_args(a);
-    AA.obs = obs_io; AA.rew = reward_io; AA.done = done_io;
-    AA.norm_obs = norm_obs_out; AA.action = action_out; AA.value = value_out; AA.logp = logp_out; AA.norm_rew = norm_reward_out;
-    AA.done_out = done_prev_out; AA.deterministic = deterministic ? 1 : 0;
-    // env step: as fwg_step, the actions come from the head phase (LDS)
-    KArgs A;
-    base_args(h, &A);
-    A.actions = nullptr; A.obs = obs_io; A.rew = reward_io; A.done = done_io; A.term = term_code_out;
-    A.term_obs = terminal_obs_out; A.metrics = metrics_out; A.tgt_out = nullptr;
-    h->last_metrics_out = metrics_out;
-    fill_slots(h, h->gstep, &A);
-    if (h->graph_mode) { A.slots_in = h->d_slots + (h->gstep & 1); A.slots_out = h->d_slots + ((h->gstep + 1) & 1); }
-    a->parity ^= 1;          // the step phase belongs to the statistics copy the head phase publishes ...
-    observer_args(h, &A);    // (... its means and counter are taken from LDS in the kernel; acc / ret / gamma from here)
-#ifdef FWG_TIMELINE
-    A.trace = h->trace;
-#endif
-    if (launch_rollout(h, a, A, AA, (hipStream_t)stream, false) != 0) {
+    const ActorArgs AA = act_args(a, obs_io, reward_io, done_io, norm_obs_out, action_out, value_out, logp_out, norm_reward_out, done_prev_out, deterministic);
+    // env step: as fwg_step, the actions come from the head phase (LDS).  The step phase belongs to the statistics copy the head
+    // phase publishes (its means and counter are taken from LDS in the kernel; acc / ret / gamma from the arguments)
+    a->parity ^= 1;
+    const KArgs A = step_args(h, nullptr, obs_io, reward_io, done_io, term_code_out, terminal_obs_out, metrics_out, nullptr);
+    if (!launch_rollout(h, a, A, AA, (hipStream_t)stream)) {
         a->parity ^= 1;
         return fail_with(FWG_ERR_INVALID, "fwg_rollout_step: no fused launch for this configuration");
     }
@@ -2876,17 +2865,21 @@ int fwg_learner_create(fwg_actor* head, fwg_learner** out) {
     fwg_learner* L = new fwg_learner();
     L->head = head;
     L->L = ppo_layout(head->D, head->act_dim);
-    HIP_TRY(hipMalloc((void**)&L->d_slab, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&L->d_grad, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
-    HIP_TRY(hipMemset(L->d_slab, 0, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
-    HIP_TRY(hipMemset(L->d_grad, 0, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
-    // (more than 64 KiB of dynamic LDS: asked for here, never inside a capture)
-    HIP_TRY(hipFuncSetAttribute((const void*)k_ppo_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ppo_grad_lds_floats() * sizeof(float))));
+    const int rc = [&]() -> int {
+        HIP_TRY(hipMalloc((void**)&L->d_slab, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&L->d_grad, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
+        HIP_TRY(hipMemset(L->d_slab, 0, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
+        HIP_TRY(hipMemset(L->d_grad, 0, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
+        // (more than 64 KiB of dynamic LDS: asked for here, never inside a capture)
+        HIP_TRY(hipFuncSetAttribute((const void*)k_ppo_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ppo_grad_lds_floats() * sizeof(float))));
+        return FWG_OK;
+    }();
+    if (rc != FWG_OK) { fwg_learner_destroy(L); return rc; }
     *out = L;
     return FWG_OK;
 }
 
-void fwg_learner_destroy(fwg_learner* L) {
+void fwg_learner_destroy(fwg_learner* L) {   // (also the failure exit of fwg_learner_create: either buffer may still be null)
     if (!L) return;
     (void)hipFree(L->d_slab); (void)hipFree(L->d_grad);
     delete L;

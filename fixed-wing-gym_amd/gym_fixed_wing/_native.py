@@ -162,15 +162,63 @@ INSTANCE_GENERIC = 100000   # FWG_INSTANCE_GENERIC (fwg_config_instance only)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libfwgym.so")
-EXPORTS = ["fwg_abi_version", "fwg_get_layout", "fwg_create", "fwg_destroy", "fwg_update_config", "fwg_seed",
-           "fwg_reset", "fwg_step", "fwg_check_actions", "fwg_reduce_success", "fwg_global_step", "fwg_last_error",
-           "fwg_dump_spec", "fwg_num_specs", "fwg_spec_index", "fwg_config_instance", "fwg_set_graph_mode", "fwg_note_replayed_steps",
-           "fwg_capture_begin", "fwg_capture_end", "fwg_capture_parity", "fwg_replay_check", "fwg_finish_episodes", "fwg_actor_create", "fwg_actor_destroy", "fwg_actor_set_weights",
-           "fwg_actor_set_stats", "fwg_actor_get_stats", "fwg_actor_configure", "fwg_actor_seed", "fwg_actor_observe",
-           "fwg_actor_act", "fwg_attach_observer", "fwg_obs_log_floats", "fwg_obs_window", "fwg_reduce_success_device",
-           "fwg_obs_gather", "fwg_actor_set_obs_log", "fwg_selftest_philox", "fwg_rollout_available", "fwg_rollout_step", "fwg_gae",
-           "fwg_learner_create", "fwg_learner_destroy", "fwg_learner_num_params", "fwg_ppo_moments", "fwg_ppo_grad", "fwg_ppo_apply",
-           "fwg_ppo_step", "fwg_actor_pack", "fwg_actor_set_conv"]
+_vp, _i64, _u64, _int, _f32 = C.c_void_p, C.c_int64, C.c_uint64, C.c_int, C.c_float
+_cfg = C.POINTER(Config)
+# every export of include/fwgym.h: name -> (restype, argtypes); handles, device pointers and streams are void pointers
+PROTOTYPES = {
+    "fwg_abi_version": (_int, []),
+    "fwg_last_error": (C.c_char_p, []),
+    "fwg_get_layout": (_int, [_cfg, C.POINTER(Layout)]),
+    "fwg_create": (_int, [_cfg, _i64, _int, _vp, _i64, C.POINTER(_vp)]),
+    "fwg_destroy": (_int, [_vp]),
+    "fwg_update_config": (_int, [_vp, _cfg]),
+    "fwg_seed": (_int, [_vp, _u64]),
+    "fwg_global_step": (_i64, [_vp]),
+    "fwg_reset": (_int, [_vp] * 6),
+    "fwg_step": (_int, [_vp] * 10),
+    "fwg_check_actions": (_int, [_vp, _vp, _vp]),
+    "fwg_finish_episodes": (_int, [_vp, _vp, _vp]),
+    "fwg_reduce_success": (_int, [_vp, C.POINTER(_f32), _vp]),
+    "fwg_reduce_success_device": (_int, [_vp, _vp, _vp]),
+    "fwg_dump_spec": (_int, [_cfg, C.POINTER(C.c_uint32), _i64]),
+    "fwg_num_specs": (_int, []),
+    "fwg_spec_index": (_int, [_vp]),
+    "fwg_config_instance": (_int, [_cfg]),
+    "fwg_set_graph_mode": (_int, [_vp, _int, _vp]),
+    "fwg_note_replayed_steps": (_int, [_vp, _i64]),
+    "fwg_capture_begin": (_int, [_vp]),
+    "fwg_capture_end": (_int, [_vp]),
+    "fwg_capture_parity": (_int, [_vp]),
+    "fwg_replay_check": (_int, [_vp, _int]),
+    "fwg_obs_log_floats": (_i64, [_cfg, _i64]),
+    "fwg_obs_window": (_int, [_vp, C.POINTER(_i64)]),
+    "fwg_obs_gather": (_int, [_vp] * 4),
+    "fwg_gae": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp]),
+    "fwg_selftest_philox": (_int, [_vp, _vp, _i64, _vp]),
+    "fwg_actor_create": (_int, [_int, _i64, _int, _int, _f32, _f32, _f32, _f32, C.POINTER(_vp)]),
+    "fwg_actor_destroy": (None, [_vp]),
+    "fwg_actor_set_weights": (_int, [_vp, C.POINTER(ActorWeights)]),
+    "fwg_actor_set_conv": (_int, [_vp, _int, _int, _vp, _vp]),
+    "fwg_actor_set_stats": (_int, [_vp, C.POINTER(ActorStats), _vp]),
+    "fwg_actor_get_stats": (_int, [_vp, C.POINTER(ActorStats), _vp]),
+    "fwg_actor_configure": (_int, [_vp, _int, _int]),
+    "fwg_actor_seed": (_int, [_vp, _u64, _i64]),
+    "fwg_actor_observe": (_int, [_vp] * 5),
+    "fwg_actor_act": (_int, [_vp] * 10 + [_int, _vp]),
+    "fwg_actor_set_obs_log": (_int, [_vp, _vp]),
+    "fwg_attach_observer": (_int, [_vp, _vp]),
+    "fwg_rollout_available": (_int, [_vp, _vp]),
+    "fwg_rollout_step": (_int, [_vp] * 14 + [_int, _vp]),
+    "fwg_learner_create": (_int, [_vp, C.POINTER(_vp)]),
+    "fwg_learner_destroy": (None, [_vp]),
+    "fwg_learner_num_params": (_i64, [_vp]),
+    "fwg_ppo_moments": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp]),
+    "fwg_ppo_grad": (_int, [_vp, C.POINTER(PpoBatch), _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "fwg_ppo_apply": (_int, [_vp, _vp, _i64] + [_vp] * 7),
+    "fwg_ppo_step": (_int, [_vp, C.POINTER(PpoBatch), _vp, _i64] + [_vp] * 8),
+    "fwg_actor_pack": (_int, [_vp, _vp, _vp]),
+}
+EXPORTS = list(PROTOTYPES)
 _libs = {}
 
 
@@ -190,95 +238,11 @@ def load_library(path=None):
     except ImportError:
         pass
     lib = C.CDLL(path)
-    for name in EXPORTS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         if not hasattr(lib, name):
             raise NativeError("{} does not export {}".format(path, name))
-    vp, i64, u64 = C.c_void_p, C.c_int64, C.c_uint64
-    lib.fwg_abi_version.restype = C.c_int
-    lib.fwg_get_layout.argtypes = [C.POINTER(Config), C.POINTER(Layout)]
-    lib.fwg_create.argtypes = [C.POINTER(Config), i64, C.c_int, vp, i64, C.POINTER(vp)]
-    lib.fwg_destroy.argtypes = [vp]
-    lib.fwg_update_config.argtypes = [vp, C.POINTER(Config)]
-    lib.fwg_seed.argtypes = [vp, u64]
-    lib.fwg_reset.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.fwg_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.fwg_check_actions.argtypes = [vp, vp, vp]
-    lib.fwg_reduce_success.argtypes = [vp, C.POINTER(C.c_float), vp]
-    lib.fwg_reduce_success_device.argtypes = [vp, vp, vp]
-    lib.fwg_reduce_success_device.restype = C.c_int
-    lib.fwg_global_step.argtypes = [vp]
-    lib.fwg_global_step.restype = i64
-    lib.fwg_last_error.restype = C.c_char_p
-    lib.fwg_dump_spec.argtypes = [C.POINTER(Config), C.POINTER(C.c_uint32), i64]
-    lib.fwg_dump_spec.restype = C.c_int
-    lib.fwg_num_specs.restype = C.c_int
-    lib.fwg_config_instance.argtypes = [C.POINTER(Config)]
-    lib.fwg_config_instance.restype = C.c_int
-    lib.fwg_spec_index.argtypes = [vp]
-    lib.fwg_spec_index.restype = C.c_int
-    lib.fwg_set_graph_mode.argtypes = [vp, C.c_int, vp]
-    lib.fwg_set_graph_mode.restype = C.c_int
-    lib.fwg_note_replayed_steps.argtypes = [vp, i64]
-    lib.fwg_note_replayed_steps.restype = C.c_int
-    lib.fwg_capture_begin.argtypes = [vp]
-    lib.fwg_capture_begin.restype = C.c_int
-    lib.fwg_capture_end.argtypes = [vp]
-    lib.fwg_capture_end.restype = C.c_int
-    lib.fwg_capture_parity.argtypes = [vp]
-    lib.fwg_capture_parity.restype = C.c_int
-    lib.fwg_replay_check.argtypes = [vp, C.c_int]
-    lib.fwg_replay_check.restype = C.c_int
-    lib.fwg_finish_episodes.argtypes = [vp, vp, vp]
-    lib.fwg_finish_episodes.restype = C.c_int
-    f32 = C.c_float
-    lib.fwg_actor_create.argtypes = [C.c_int, i64, C.c_int, C.c_int, f32, f32, f32, f32, C.POINTER(vp)]
-    lib.fwg_actor_destroy.argtypes = [vp]
-    lib.fwg_actor_destroy.restype = None
-    lib.fwg_actor_set_weights.argtypes = [vp, C.POINTER(ActorWeights)]
-    lib.fwg_actor_set_conv.argtypes = [vp, C.c_int, C.c_int, vp, vp]
-    lib.fwg_actor_set_stats.argtypes = [vp, C.POINTER(ActorStats), vp]
-    lib.fwg_actor_get_stats.argtypes = [vp, C.POINTER(ActorStats), vp]
-    lib.fwg_actor_configure.argtypes = [vp, C.c_int, C.c_int]
-    lib.fwg_actor_seed.argtypes = [vp, u64, i64]
-    lib.fwg_actor_observe.argtypes = [vp, vp, vp, vp, vp]
-    lib.fwg_obs_log_floats.argtypes = [C.POINTER(Config), i64]
-    lib.fwg_obs_log_floats.restype = i64
-    lib.fwg_obs_window.argtypes = [vp, C.POINTER(i64)]
-    lib.fwg_obs_window.restype = C.c_int
-    lib.fwg_selftest_philox.argtypes = [vp, vp, i64, vp]
-    lib.fwg_selftest_philox.restype = C.c_int
-    lib.fwg_obs_gather.argtypes = [vp, vp, vp, vp]
-    lib.fwg_obs_gather.restype = C.c_int
-    lib.fwg_actor_set_obs_log.argtypes = [vp, vp]
-    lib.fwg_actor_set_obs_log.restype = C.c_int
-    lib.fwg_attach_observer.argtypes = [vp, vp]
-    lib.fwg_attach_observer.restype = C.c_int
-    lib.fwg_actor_act.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp]
-    lib.fwg_rollout_available.argtypes = [vp, vp]
-    lib.fwg_rollout_available.restype = C.c_int
-    lib.fwg_rollout_step.argtypes = [vp, vp] + [vp] * 12 + [C.c_int, vp]
-    lib.fwg_rollout_step.restype = C.c_int
-    lib.fwg_gae.argtypes = [i64, i64, vp, vp, vp, vp, f32, f32, vp, vp, vp]
-    lib.fwg_gae.restype = C.c_int
-    lib.fwg_learner_create.argtypes = [vp, C.POINTER(vp)]
-    lib.fwg_learner_create.restype = C.c_int
-    lib.fwg_learner_destroy.argtypes = [vp]
-    lib.fwg_learner_destroy.restype = None
-    lib.fwg_learner_num_params.argtypes = [vp]
-    lib.fwg_learner_num_params.restype = i64
-    lib.fwg_ppo_moments.argtypes = [vp, vp, vp, i64, C.c_int, vp, vp]
-    lib.fwg_ppo_grad.argtypes = [vp, C.POINTER(PpoBatch), vp, i64, vp, vp, vp, vp, vp]
-    lib.fwg_ppo_apply.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
-    lib.fwg_ppo_step.argtypes = [vp, C.POINTER(PpoBatch), vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.fwg_actor_pack.argtypes = [vp, vp, vp]
-    for name in ("fwg_ppo_moments", "fwg_ppo_grad", "fwg_ppo_apply", "fwg_ppo_step", "fwg_actor_pack"):
-        getattr(lib, name).restype = C.c_int
-    for name in ("fwg_actor_create", "fwg_actor_set_weights", "fwg_actor_set_conv", "fwg_actor_set_stats", "fwg_actor_get_stats",
-                 "fwg_actor_configure", "fwg_actor_seed", "fwg_actor_observe", "fwg_actor_act"):
-        getattr(lib, name).restype = C.c_int
-    for name in ("fwg_get_layout", "fwg_create", "fwg_destroy", "fwg_update_config", "fwg_seed", "fwg_reset",
-                 "fwg_step", "fwg_check_actions", "fwg_reduce_success"):
-        getattr(lib, name).restype = C.c_int
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.fwg_abi_version() != FWG_ABI_VERSION:
         raise NativeError("ABI mismatch: library {} vs binding {}".format(lib.fwg_abi_version(), FWG_ABI_VERSION))
     _libs[path] = lib

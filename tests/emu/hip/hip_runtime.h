@@ -44,8 +44,18 @@ enum { hipSuccess = 0 };
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
 static inline const char* hipGetErrorString(hipError_t) { return "emu"; }
 static inline hipError_t hipSetDevice(int) { return 0; }
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = calloc(1, n); return 0; }
-static inline hipError_t hipFree(void* p) { free(p); return 0; }
+// (allocations are counted, and the k-th next hipMalloc can be made to fail: tests/test_host_lifecycle.py checks that a create
+// whose allocation fails gives everything back)
+static long emu_live_allocs = 0, emu_malloc_countdown = 0;
+extern "C" long emu_hip_live_allocations(void) { return emu_live_allocs; }
+extern "C" void emu_hip_fail_malloc(long kth) { emu_malloc_countdown = kth; }   // kth = 1: the next one; 0: none
+static inline hipError_t hipMalloc(void** p, size_t n) {
+    if (emu_malloc_countdown > 0 && --emu_malloc_countdown == 0) { *p = nullptr; return 2; }
+    *p = calloc(1, n);
+    ++emu_live_allocs;
+    return 0;
+}
+static inline hipError_t hipFree(void* p) { if (p) --emu_live_allocs; free(p); return 0; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return 0; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return 0; }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { memset(d, v, n); return 0; }

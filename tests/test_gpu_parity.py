@@ -190,11 +190,11 @@ def test_full_size_properties():
         np.testing.assert_array_equal(hist[11][0][alive, k, :], hist[11 - 2 * k][0][alive, 0, :])
 
 
-def test_success_reduction_matches_infos():
+@pytest.mark.parametrize("n", [1, 65, 1000])   # k_finish: one valid lane; a second block with one valid lane; a partial last wave
+def test_success_reduction_matches_infos(n):
     cfg = configs.reference_like("default")
     ckw = {"steps_max": 30, "target": {"success_streak_req": 5, "success_streak_fraction": 0.6,
                                        "states": {0: {"bound": 100}, 1: {"bound": 45}, 2: {"bound": 12}}}}
-    n = 1000
     vec = _vec(cfg, n, config_kw=ckw, seed=4, as_numpy=True)
     vec.reset()
     rng = np.random.default_rng(0)
