@@ -2,7 +2,7 @@
 """Train a PPO attitude controller on the MI355X-native env -- the reference's examples/train_rl_controller.py
 (`VecNormalize(SubprocVecEnv(...))` + `PPO2(MlpPolicy, env).learn(5e6, callback=monitor_training)` with the curriculum rule of
 its callback, :80-87) with the whole data path on the device: rollouts by the HIP head + env step kernels, advantages by fwg_gae,
-the PPO2 update in torch on the same buffers (or, with --update hip, as HIP kernels: gym_fixed_wing/learner.py), the success sums all-gathered over RCCL, the curriculum raised on every rank.
+the PPO2 update in torch on the same buffers (or, with --update hip, as HIP kernels for either policy: gym_fixed_wing/learner.py), the success sums all-gathered over RCCL, the curriculum raised on every rank.
 
     python examples/train_ppo.py --envs 4096 --timesteps 100e6 --out model.npz
     python examples/train_ppo.py --policy cnn --envs 4096 --timesteps 100e6 --out cnn_model.npz   (the CNN controller)
@@ -34,7 +34,8 @@ from gym_fixed_wing.rollout import CnnMlpPolicy  # noqa: E402
 def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, learning_rate=5e-4, n_steps=128, curriculum=True,
           config=None, log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch", policy="mlp"):
     """policy: "mlp" (MlpPolicy on the examples config's 12-vector) or "cnn" (CnnMlpPolicy on the cnn config's 5 x 12 matrix
-    observations: the reference's --policy CNN, train_rl_controller.py:179-197).  config: preset name, default by policy."""
+    observations: the reference's --policy CNN, train_rl_controller.py:179-197).  update: "torch" or "hip" (for the cnn policy
+    "hip" is PPO's "hip_cnn").  config: preset name, default by policy."""
     config = config or ("cnn" if policy == "cnn" else "examples")
     # (the cnn configuration's build-time kernel instance is the shipped one, derived views on: presets.SPECIALISED ship_cnn_log)
     vec = make_sharded_env(presets.preset(config), total_envs=envs, rank=rank, world_size=world, device=local,
@@ -46,6 +47,8 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
     if policy == "cnn":
         torch.manual_seed(seed)
         net = sb_init_(CnnMlpPolicy(obs_shape=vec.obs_shape, n_filters=3))
+    if policy == "cnn" and update == "hip":
+        update = "hip_cnn"
     ppo = PPO(vec, policy=net, seed=seed, curriculum=sched, n_steps=n_steps, nminibatches=nminibatches, noptepochs=noptepochs,
               learning_rate=learning_rate, fused=fused, ent_coef=ent_coef, update=update)
     t0 = time.perf_counter()
@@ -80,7 +83,7 @@ def main():
     ap.add_argument("--disable-curriculum", action="store_true")
     ap.add_argument("--update", choices=("torch", "hip"), default="torch", help="PPO update: torch autograd (default) or the HIP kernels")
     ap.add_argument("--policy", choices=("mlp", "cnn"), default="mlp",
-                    help="mlp: MlpPolicy, examples config; cnn: CnnMlpPolicy (3 filters), cnn config (torch update only)")
+                    help="mlp: MlpPolicy, examples config; cnn: CnnMlpPolicy (3 filters), cnn config (either update)")
     ap.add_argument("--out", default=None, help="save weights + VecNormalize statistics (.npz)")
     ap.add_argument("--curve", default=None, help="write the learning curve (JSON)")
     args = ap.parse_args()

@@ -2847,7 +2847,8 @@ static int ppo_launch_grad(fwg_learner* L, const fwg_ppo_batch* b, const int64_t
     G.hp = (const PpoHparams*)hp; G.slab = L->d_slab; G.L = L->L;
     G.ntiles = (long)((mb + FWG_PPO_ROWS - 1) / FWG_PPO_ROWS);
     const unsigned nb = (unsigned)(G.ntiles < FWG_PPO_MAX_BLOCKS ? G.ntiles : FWG_PPO_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_ppo_grad, dim3(nb), dim3(FWG_PPO_THREADS), (size_t)ppo_grad_lds_floats() * sizeof(float), st, G);
+    if (L->L.cnn) hipLaunchKernelGGL((k_ppo_grad<true>), dim3(nb), dim3(FWG_PPO_THREADS), (size_t)ppo_grad_lds_floats(true) * sizeof(float), st, G);
+    else hipLaunchKernelGGL((k_ppo_grad<false>), dim3(nb), dim3(FWG_PPO_THREADS), (size_t)ppo_grad_lds_floats() * sizeof(float), st, G);
     HIP_TRY(hipGetLastError());
     const int n = L->L.P + FWG_PPO_NSTAT;
     hipLaunchKernelGGL(k_ppo_reduce, dim3((unsigned)((n + FWG_PPO_THREADS - 1) / FWG_PPO_THREADS)), dim3(FWG_PPO_THREADS), 0, st,
@@ -2856,27 +2857,39 @@ static int ppo_launch_grad(fwg_learner* L, const fwg_ppo_batch* b, const int64_t
     return FWG_OK;
 }
 
-extern "C" {
-
-int fwg_learner_create(fwg_actor* head, fwg_learner** out) {
-    if (!head || !out) return fail_with(FWG_ERR_INVALID, "fwg_learner_create: null argument");
-    if (head->cnn_filters) return fail_with(FWG_ERR_INVALID, "fwg_learner_create: the HIP PPO update has no backward pass through the conv of a CNN head");
+// fwg_learner_create (cnn = false) / fwg_learner_create_cnn: the head's kind was checked by the caller
+static int learner_create(fwg_actor* head, bool cnn, fwg_learner** out) {
     HIP_TRY(hipSetDevice(head->device));
     fwg_learner* L = new fwg_learner();
     L->head = head;
-    L->L = ppo_layout(head->D, head->act_dim);
+    L->L = ppo_layout(head->D, head->act_dim, cnn);
     const int rc = [&]() -> int {
         HIP_TRY(hipMalloc((void**)&L->d_slab, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
         HIP_TRY(hipMalloc((void**)&L->d_grad, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
         HIP_TRY(hipMemset(L->d_slab, 0, (size_t)FWG_PPO_MAX_BLOCKS * L->L.SW * sizeof(float)));
         HIP_TRY(hipMemset(L->d_grad, 0, (size_t)(L->L.P + FWG_PPO_NSTAT) * sizeof(float)));
         // (more than 64 KiB of dynamic LDS: asked for here, never inside a capture)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_ppo_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ppo_grad_lds_floats() * sizeof(float))));
+        if (cnn) HIP_TRY(hipFuncSetAttribute((const void*)k_ppo_grad<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ppo_grad_lds_floats(true) * sizeof(float))));
+        else HIP_TRY(hipFuncSetAttribute((const void*)k_ppo_grad<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ppo_grad_lds_floats() * sizeof(float))));
         return FWG_OK;
     }();
     if (rc != FWG_OK) { fwg_learner_destroy(L); return rc; }
     *out = L;
     return FWG_OK;
+}
+
+extern "C" {
+
+int fwg_learner_create(fwg_actor* head, fwg_learner** out) {
+    if (!head || !out) return fail_with(FWG_ERR_INVALID, "fwg_learner_create: null argument");
+    if (head->cnn_filters) return fail_with(FWG_ERR_INVALID, "fwg_learner_create: this learner has no backward pass through the conv of a CNN head; use fwg_learner_create_cnn");
+    return learner_create(head, false, out);
+}
+
+int fwg_learner_create_cnn(fwg_actor* head, fwg_learner** out) {
+    if (!head || !out) return fail_with(FWG_ERR_INVALID, "fwg_learner_create_cnn: null argument");
+    if (!head->cnn_filters) return fail_with(FWG_ERR_INVALID, "fwg_learner_create_cnn: the head is an MLP head (no fwg_actor_set_conv); use fwg_learner_create");
+    return learner_create(head, true, out);
 }
 
 void fwg_learner_destroy(fwg_learner* L) {   // (also the failure exit of fwg_learner_create: either buffer may still be null)
@@ -2926,7 +2939,8 @@ int fwg_ppo_step(fwg_learner* L, const fwg_ppo_batch* b, const int64_t* idx, int
 int fwg_actor_pack(fwg_learner* L, const float* params, void* stream) {
     if (!L || !params) return fail_with(FWG_ERR_INVALID, "fwg_actor_pack: null argument");
     const fwg_actor* a = L->head;
-    const int n = 2 * actor_frags(a->nk1) * 64 + 2 * FWG_ACT_BIAS_FLOATS + FWG_ACT_MAX_ACT;
+    if ((a->cnn_filters != 0) != (L->L.cnn != 0)) return fail_with(FWG_ERR_INVALID, "fwg_actor_pack: the head changed between MLP and CNN since the learner was created");
+    const int n = 2 * actor_frags(a->nk1) * 64 + 2 * FWG_ACT_BIAS_FLOATS + FWG_ACT_MAX_ACT + (L->L.cnn ? FWG_CNN_PARAMS : 0);
     hipLaunchKernelGGL(k_actor_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, L->L, a->nk1,
                        a->d_frags, a->d_bias, a->d_log_std);
     HIP_TRY(hipGetLastError());

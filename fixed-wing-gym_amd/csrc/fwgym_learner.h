@@ -11,6 +11,11 @@
 //   k_actor_pack  : the head's operand fragments / biases / log-std (fwg_actor_set_weights' packing) from the flat parameters
 // Parameters, gradients and Adam moments share one flat fp32 layout, MlpPolicy.parameters() order:
 //   log_std | pi.0.weight pi.0.bias pi.2.weight pi.2.bias pi.4.weight pi.4.bias | vf.0.weight ... vf.4.bias
+// and for the CNN head's CnnMlpPolicy (fwg_learner_create_cnn, k_ppo_grad<true>), CnnMlpPolicy.parameters() order:
+//   log_std | conv.weight [5][3] conv.bias [3] | pi.1.weight [64][36] pi.1.bias ... pi.5.bias | vf.1.weight ... vf.5.bias
+// The conv (one module shared by pi and vf) runs on the VALU: C = tanh(conv(X)) in a sixth LDS tile is the networks' input, the
+// two networks' dL / dC add up in one accumulator carried over the per-network loop, and the 18 conv gradients are per-lane
+// partial sums over the workgroup's tiles, reduced in a fixed order at the end.
 // The GEMMs run on v_mfma_f32_32x32x16_bf16 with every fp32 operand split x = hi + lo (three products, fwgym_actor.h).  A tile's
 // activations sit in LDS row-major (stride FWG_PPO_LS, odd: row-strided lane reads hit distinct banks); each of the four waves
 // owns one 32x32 quarter of every 64x64 product, so the weight-gradient GEMMs (contraction over the tile's rows) accumulate in
@@ -28,17 +33,23 @@
 // (double: the values torch.optim.Adam / clip_grad_norm_ compute their scalars from -- 1 - beta2 of a float beta2 is off by 1e-5)
 struct PpoHparams { double lr, cliprange, ent_coef, vf_coef, max_grad_norm, beta1, beta2, eps; };
 // offsets into the flat parameter vector; [net] 0 = pi, 1 = vf.  P parameters, SW floats per slab (P + the loss sums, padded)
-struct PpoLayout { int D, A, P, SW; int ls, w1[2], b1[2], w2[2], b2[2], w3[2], b3[2]; };
+// K1: layer 0's fan-in (D; the CNN's 36 conv outputs).  cnn: 1 = the conv's weight [5][3] at cw and bias [3] at cb
+struct PpoLayout { int D, A, P, SW; int ls, w1[2], b1[2], w2[2], b2[2], w3[2], b3[2]; int K1, cnn, cw, cb; };
 struct PpoBatch { const float *obs, *act, *val, *logp, *adv, *ret; };
 
-__host__ __device__ inline PpoLayout ppo_layout(int D, int A) {
+__host__ __device__ inline PpoLayout ppo_layout(int D, int A, bool cnn = false) {
     PpoLayout L;
     L.D = D; L.A = A;
+    L.K1 = cnn ? FWG_CNN_K : D; L.cnn = cnn ? 1 : 0; L.cw = L.cb = 0;
     int o = 0;
     L.ls = o; o += A;
+    if (cnn) {
+        L.cw = o; o += FWG_CNN_ROWS * FWG_CNN_FILTERS;
+        L.cb = o; o += FWG_CNN_FILTERS;
+    }
     for (int net = 0; net < 2; ++net) {
         const int nout = net ? 1 : A;
-        L.w1[net] = o; o += 64 * D;
+        L.w1[net] = o; o += 64 * L.K1;
         L.b1[net] = o; o += 64;
         L.w2[net] = o; o += 64 * 64;
         L.b2[net] = o; o += 64;
@@ -56,10 +67,14 @@ __device__ __forceinline__ float ppo_tanh(float z) { return tanh_prescaled(FWG_A
 // acc += sum_k A(m, k) B(k, n) for the calling wave's 32 x 32 tile (m0, n0), A(m, k) = A[m sam + k sak], B(k, n) = B[k sbk + n sbn],
 // k over [0, K) in 16-wide blocks; entries with m >= ml, k >= kl or n >= nl read as 0 (and are not addressed).  Lane l
 // supplies A row / B column l & 31 and k-slots 8 (l >> 5) + t; it receives rows (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31.
+// ROLLED (the CNN instance of k_ppo_grad): two k-blocks unrolled instead of all -- with every block's operand loads hoisted the
+// CNN instance needs more than the 512 registers of a lane; the default leaves the MLP instance's code as it was
+template <bool ROLLED = false>
 __device__ __forceinline__ void ppo_mma_tile(f32x16& acc, const float* A, int sam, int sak, int m0, int ml, const float* B, int sbk,
                                              int sbn, int n0, int nl, int K, int kl, int l) {
     const int i = l & 31, half = l >> 5;
     const bool mok = m0 + i < ml, nok = n0 + i < nl;
+#pragma unroll (ROLLED ? 2 : 8)
     for (int k0 = 0; k0 < K; k0 += 16) {
         float a[8], b[8];
 #pragma unroll
@@ -127,9 +142,21 @@ struct PpoGradArgs {
     float* slab;                // [gridDim.x][SW]
     PpoLayout L;
 };
-__host__ __device__ inline int ppo_grad_lds_floats() { return 5 * FWG_PPO_ROWS * FWG_PPO_LS + 4 * FWG_PPO_ROWS + 8 * FWG_PPO_ROWS + 8 * FWG_PPO_ROWS; }
+// (CNN: one more tile, the conv outputs)
+__host__ __device__ inline int ppo_grad_lds_floats(bool cnn = false) {
+    return (cnn ? 6 : 5) * FWG_PPO_ROWS * FWG_PPO_LS + 4 * FWG_PPO_ROWS + 8 * FWG_PPO_ROWS + 8 * FWG_PPO_ROWS;
+}
+#define FWG_PPO_CNN_SUMS (FWG_CNN_ROWS * FWG_CNN_FILTERS + FWG_CNN_FILTERS)   // conv gradients: dW [5][3], then db [3]
+#define FWG_PPO_CNN_PARTS 8                                                   // ... each summed by 8 lanes, 8 rows of a tile each
 
+// CNN = true: the CnnMlpPolicy's instance.  Its loops are unrolled by 8 / 2 (`CNN ? 8 : 64`: 64 = all of it, the MLP instance's
+// code is what it was before the template): 248-256 VGPRs, no scratch, no spills (gym_fixed_wing/kernel_resources.json)
+template <bool CNN>
 __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs G) {
+    // (the backward pass below differentiates tanh, and both passes index the conv outputs feature-major)
+    static_assert(!CNN || (FWG_CNN_ACTIVATION == FWG_CNN_ACT_TANH && FWG_CNN_FEATURE_MAJOR == 1), "k_ppo_grad<true>: tanh after the conv, k = j * FILTERS + c");
+    static_assert(FWG_PPO_CNN_SUMS * FWG_PPO_CNN_PARTS <= FWG_PPO_THREADS && FWG_PPO_CNN_SUMS * FWG_PPO_CNN_PARTS <= 8 * FWG_PPO_ROWS &&
+                  FWG_CNN_ROWS * FWG_CNN_COLS <= 64 && FWG_CNN_K <= 64, "conv gradient lanes / reduction space / tile width");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int LS = FWG_PPO_LS;
     const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6, half = l >> 5;
@@ -143,6 +170,7 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
     float* dO = Tb + FWG_PPO_ROWS * LS;     // [64][4] network outputs, then dL / d(output)
     float* rowf = dO + 4 * FWG_PPO_ROWS;    // [64][8] action[4], old value, old log-prob, normalised advantage, return
     float* red = rowf + 8 * FWG_PPO_ROWS;   // [64][8] end-of-block reduction of the per-row sums
+    float* Cs = red + 8 * FWG_PPO_ROWS;     // (CNN) [64][LS] conv outputs of the tile, k = feature * FILTERS + filter
     const PpoHparams hp = *G.hp;
     const float adv_mean = G.mom[0], adv_std = G.mom[1];
     const float inv_mb = 1.f / (float)G.mb, clip = (float)hp.cliprange, vf_coef = (float)hp.vf_coef;
@@ -155,6 +183,9 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
     for (int r = 0; r < 16; ++r) { gw1[0][r] = 0.f; gw1[1][r] = 0.f; gw2[0][r] = 0.f; gw2[1][r] = 0.f; }
     float gw3[2] = {0.f, 0.f}, gb3[2] = {0.f, 0.f}, gb2[2] = {0.f, 0.f}, gb1[2] = {0.f, 0.f};
     float gls[FWG_ACT_MAX_ACT] = {0.f, 0.f, 0.f, 0.f}, st[FWG_PPO_NSTAT] = {0.f, 0.f, 0.f, 0.f};
+    // (CNN) conv gradient `cs` (r * FILTERS + c: dW[r][c]; ROWS * FILTERS + c: db[c]) over the tile rows 8 cp .. 8 cp + 7
+    const int cs = tid / FWG_PPO_CNN_PARTS, cp = tid % FWG_PPO_CNN_PARTS;
+    float gcv = 0.f;
     for (long t = t0; t < t1; ++t) {
         const long r0 = t * FWG_PPO_ROWS;
         const int nrows = (int)(G.mb - r0 < FWG_PPO_ROWS ? G.mb - r0 : FWG_PPO_ROWS);
@@ -173,6 +204,19 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
             }
         }
         __syncthreads();
+        f32x16 dc = {0.f};   // (CNN) dL / dC of this wave's quarter, both networks
+        if constexpr (CNN) {   // C = tanh(conv(X)): 64 rows x 36 outputs, nine per thread (rows past the minibatch: X = 0)
+            const float *cw = P + L.cw, *cb = P + L.cb;
+#pragma unroll 1
+            for (int e = tid; e < FWG_PPO_ROWS * FWG_CNN_K; e += FWG_PPO_THREADS) {
+                const int r = e / FWG_CNN_K, k = e % FWG_CNN_K, j = cnn_feature(k), c = cnn_filter(k);
+                float z = cb[c];
+#pragma unroll
+                for (int q = 0; q < FWG_CNN_ROWS; ++q) z = fmaf(cw[q * FWG_CNN_FILTERS + c], Xs[r * LS + q * FWG_CNN_COLS + j], z);
+                Cs[r * LS + k] = ppo_tanh(z);
+            }
+            __syncthreads();
+        }
 #pragma unroll
         for (int net = 0; net < 2; ++net) {   // (unrolled: the per-network accumulators stay in registers)
             const int nout = net ? 1 : A;
@@ -180,7 +224,9 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
             const float *W3 = P + L.w3[net], *b3 = P + L.b3[net];
             {   // layer 1: H1 = tanh(X W1^T + b1)
                 f32x16 acc = {0.f};
-                ppo_mma_tile(acc, Xs, LS, 1, tm0, 64, W1, 1, D, tn0, 64, 16 * nk1, D, l);
+                if constexpr (CNN) ppo_mma_tile<CNN>(acc, Cs, LS, 1, tm0, 64, W1, 1, FWG_CNN_K, tn0, 64, 16 * FWG_CNN_NK1, FWG_CNN_K, l);
+                else
+                ppo_mma_tile<CNN>(acc, Xs, LS, 1, tm0, 64, W1, 1, D, tn0, 64, 16 * nk1, D, l);
                 const int n = tn0 + (l & 31);
                 const float bn = b1[n];
 #pragma unroll
@@ -189,7 +235,7 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
             __syncthreads();
             {   // layer 2: H2 = tanh(H1 W2^T + b2)
                 f32x16 acc = {0.f};
-                ppo_mma_tile(acc, H1, LS, 1, tm0, 64, W2, 1, 64, tn0, 64, 64, 64, l);
+                ppo_mma_tile<CNN>(acc, H1, LS, 1, tm0, 64, W2, 1, 64, tn0, 64, 64, 64, l);
                 const int n = tn0 + (l & 31);
                 const float bn = b2[n];
 #pragma unroll
@@ -198,6 +244,7 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
             __syncthreads();
             if (vo < nout) {   // output layer (act_dim <= 4 / 1 columns: VALU), row vk
                 float o = b3[vo];
+#pragma unroll (CNN ? 8 : 64)
                 for (int k = 0; k < 64; ++k) o += H2[vk * LS + k] * W3[vo * 64 + k];
                 dO[vk * 4 + vo] = o;
             }
@@ -251,11 +298,13 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
             // ---- backward: output layer (VALU)
             if (vo < nout) {
                 float s = 0.f, sb = 0.f;
+#pragma unroll (CNN ? 8 : 64)
                 for (int r = 0; r < FWG_PPO_ROWS; ++r) { s += dO[r * 4 + vo] * H2[r * LS + vk]; sb += dO[r * 4 + vo]; }
                 gw3[net] += s;
                 if (vk == 0) gb3[net] += sb;
             }
             // G2 = (dO W3) * (1 - H2^2)
+#pragma unroll (CNN ? 8 : 64)
             for (int j = 0; j < FWG_PPO_ROWS * 64 / FWG_PPO_THREADS; ++j) {
                 const int e = tid + FWG_PPO_THREADS * j, r = e >> 6, k = e & 63;
                 float s = 0.f;
@@ -266,7 +315,7 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
             __syncthreads();
             {   // G1 = (G2 W2) * (1 - H1^2);  dW2 += G2^T H1 (contraction over the tile's rows);  db2
                 f32x16 acc = {0.f};
-                ppo_mma_tile(acc, Gb, LS, 1, tm0, 64, W2, 64, 1, tn0, 64, 64, 64, l);
+                ppo_mma_tile<CNN>(acc, Gb, LS, 1, tm0, 64, W2, 64, 1, tn0, 64, 64, 64, l);
                 const int n = tn0 + (l & 31);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
@@ -274,22 +323,51 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
                     const float h = H1[m * LS + n];
                     Tb[m * LS + n] = acc[r] * (1.f - h * h);
                 }
-                ppo_mma_tile(gw2[net], Gb, 1, LS, tm0, 64, H1, LS, 1, tn0, 64, 64, 64, l);
+                ppo_mma_tile<CNN>(gw2[net], Gb, 1, LS, tm0, 64, H1, LS, 1, tn0, 64, 64, 64, l);
                 if (tid < 64) {
                     float s = 0.f;
+#pragma unroll (CNN ? 8 : 64)
                     for (int r = 0; r < FWG_PPO_ROWS; ++r) s += Gb[r * LS + tid];
                     gb2[net] += s;
                 }
             }
             __syncthreads();
-            // dW1 += G1^T X;  db1
-            if (tn0 < D) ppo_mma_tile(gw1[net], Tb, 1, LS, tm0, 64, Xs, LS, 1, tn0, D, 64, 64, l);
+            // dW1 += G1^T X;  db1  (CNN: G1^T C, and dC += G1 W1 -- the conv is shared, the two networks' terms add)
+            if constexpr (CNN) {
+                ppo_mma_tile<CNN>(gw1[net], Tb, 1, LS, tm0, 64, Cs, LS, 1, tn0, FWG_CNN_K, 64, 64, l);
+                ppo_mma_tile<CNN>(dc, Tb, LS, 1, tm0, 64, W1, FWG_CNN_K, 1, tn0, FWG_CNN_K, 64, 64, l);
+            } else
+            if (tn0 < D) ppo_mma_tile<CNN>(gw1[net], Tb, 1, LS, tm0, 64, Xs, LS, 1, tn0, D, 64, 64, l);
             if (tid < 64) {
                 float s = 0.f;
+#pragma unroll (CNN ? 8 : 64)
                 for (int r = 0; r < FWG_PPO_ROWS; ++r) s += Tb[r * LS + tid];
                 gb1[net] += s;
             }
             __syncthreads();
+        }
+        if constexpr (CNN) {   // dZ = dC * (1 - C^2) into Gb (free by now), then the conv's gradients: contraction over rows and features
+            const int n = tn0 + (l & 31);
+            if (n < FWG_CNN_K) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = tm0 + ppo_acc_row(r, half);
+                    const float c = Cs[m * LS + n];
+                    Gb[m * LS + n] = dc[r] * (1.f - c * c);
+                }
+            }
+            __syncthreads();
+            if (cs < FWG_PPO_CNN_SUMS) {
+                const bool isw = cs < FWG_CNN_ROWS * FWG_CNN_FILTERS;
+                const int q = isw ? cs / FWG_CNN_FILTERS : 0, c = isw ? cs % FWG_CNN_FILTERS : cs - FWG_CNN_ROWS * FWG_CNN_FILTERS;
+                float s = 0.f;
+#pragma unroll 1
+                for (int r = FWG_PPO_ROWS / FWG_PPO_CNN_PARTS * cp; r < FWG_PPO_ROWS / FWG_PPO_CNN_PARTS * (cp + 1); ++r)
+                    for (int j = 0; j < FWG_CNN_COLS; ++j)
+                        s += Gb[r * LS + j * FWG_CNN_FILTERS + c] * (isw ? Xs[r * LS + q * FWG_CNN_COLS + j] : 1.f);
+                gcv += s;
+            }
+            __syncthreads();   // (the next tile's gather writes Xs)
         }
     }
     // ---- the workgroup's slab: every entry written by exactly one lane
@@ -301,6 +379,7 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = tm0 + ppo_acc_row(r, half);
+            if constexpr (CNN) { if (n < FWG_CNN_K) S[L.w1[net] + m * FWG_CNN_K + n] = gw1[net][r]; } else
             if (n < D) S[L.w1[net] + m * D + n] = gw1[net][r];
             S[L.w2[net] + m * 64 + n] = gw2[net][r];
         }
@@ -320,6 +399,16 @@ __global__ __launch_bounds__(FWG_PPO_THREADS) void k_ppo_grad(const PpoGradArgs 
         for (int r = 0; r < FWG_PPO_ROWS; ++r) s += red[r * 8 + tid];
         if (tid < A) S[L.ls + tid] = s;
         else if (tid >= 4) S[L.P + tid - 4] = s;
+    }
+    if constexpr (CNN) {   // the conv's 18 gradients: the 8 lanes' partial sums in lane order (conv.weight and conv.bias are adjacent)
+        __syncthreads();
+        if (cs < FWG_PPO_CNN_SUMS) red[tid] = gcv;
+        __syncthreads();
+        if (tid < FWG_PPO_CNN_SUMS) {
+            float s = 0.f;
+            for (int p = 0; p < FWG_PPO_CNN_PARTS; ++p) s += red[tid * FWG_PPO_CNN_PARTS + p];
+            S[L.cw + tid] = s;
+        }
     }
 }
 
@@ -388,7 +477,7 @@ __global__ __launch_bounds__(FWG_PPO_APPLY_THREADS) void k_ppo_apply(const float
 // ---------------------------------------------------------------------------------------------------------------------
 // k_actor_pack: fwg_actor_set_weights' packing (actor_pack_layer / actor_pack_bias) on the device, from the flat parameters.
 // Thread = (net, fragment, lane) of frags [net][part hi/lo][frag][64]; the last 2 x FWG_ACT_BIAS_FLOATS + 4 threads write the
-// biases and the log-std
+// biases and the log-std; for a CNN layout FWG_CNN_PARAMS more write the conv behind the biases (fwg_actor_set_conv's layout)
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_actor_pack(const float* __restrict__ params, const PpoLayout L, int nk1, frag_t* __restrict__ frags,
                                                     float* __restrict__ bias, float* __restrict__ log_std) {
@@ -402,7 +491,7 @@ __global__ __launch_bounds__(256) void k_actor_pack(const float* __restrict__ pa
         int out, in, it, kk;
         bool chained;
         float scale;
-        if (f < 2 * nk1) { W = params + L.w1[net]; out = 64; in = L.D; it = f / nk1; kk = f % nk1; chained = false; scale = FWG_ACT_PRESCALE; }
+        if (f < 2 * nk1) { W = params + L.w1[net]; out = 64; in = L.K1; it = f / nk1; kk = f % nk1; chained = false; scale = FWG_ACT_PRESCALE; }
         else if (f < 2 * nk1 + 8) { W = params + L.w2[net]; out = 64; in = 64; it = (f - 2 * nk1) / 4; kk = (f - 2 * nk1) % 4; chained = true; scale = FWG_ACT_PRESCALE; }
         else { W = params + L.w3[net]; out = nout; in = 64; it = 0; kk = f - 2 * nk1 - 8; chained = true; scale = 1.f; }
         const int i = 32 * it + (l & 31);
@@ -431,5 +520,8 @@ __global__ __launch_bounds__(256) void k_actor_pack(const float* __restrict__ pa
     } else if (j < 2 * FWG_ACT_BIAS_FLOATS + FWG_ACT_MAX_ACT) {
         const int a = j - 2 * FWG_ACT_BIAS_FLOATS;
         log_std[a] = a < L.A ? params[L.ls + a] : 0.f;
+    } else if (L.cnn && j < 2 * FWG_ACT_BIAS_FLOATS + FWG_ACT_MAX_ACT + FWG_CNN_PARAMS) {
+        const int i = j - 2 * FWG_ACT_BIAS_FLOATS - FWG_ACT_MAX_ACT;   // w[r][c] at r FILTERS + c, then b[c] (adjacent in the flat layout too)
+        bias[2 * FWG_ACT_BIAS_FLOATS + i] = i < FWG_PPO_CNN_SUMS ? params[L.cw + i] : 0.f;
     }
 }

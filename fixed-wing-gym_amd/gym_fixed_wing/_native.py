@@ -3,7 +3,7 @@ module without a built library raises, there is no CPU fallback."""
 import ctypes as C
 import os
 
-FWG_ABI_VERSION = 22
+FWG_ABI_VERSION = 23
 N_VARS = 23
 N_RESET_VARS = 21
 N_PARAMS = 49
@@ -210,6 +210,7 @@ PROTOTYPES = {
     "fwg_rollout_available": (_int, [_vp, _vp]),
     "fwg_rollout_step": (_int, [_vp] * 14 + [_int, _vp]),
     "fwg_learner_create": (_int, [_vp, C.POINTER(_vp)]),
+    "fwg_learner_create_cnn": (_int, [_vp, C.POINTER(_vp)]),
     "fwg_learner_destroy": (None, [_vp]),
     "fwg_learner_num_params": (_i64, [_vp]),
     "fwg_ppo_moments": (_int, [_vp, _vp, _vp, _i64, _int, _vp, _vp]),

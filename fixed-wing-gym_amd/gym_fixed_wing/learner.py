@@ -1,10 +1,10 @@
-"""The two PPO updaters behind PPO(update="torch" | "hip"): stable-baselines PPO2's minibatch step -- loss, backward,
+"""The two PPO updaters behind PPO(update="torch" | "hip" | "hip_cnn"): stable-baselines PPO2's minibatch step -- loss, backward,
 clip_grad_norm_, Adam -- by torch autograd (TorchUpdater) or as HIP kernels (HipLearner; include/fwgym.h "PPO update").  Both have
 update(batch, perms, mb, nmb, lr, cliprange, ent_coef, vf_coef, max_grad_norm, world=1, group=None) -> {stat: mean over the steps}:
 `perms` yields one permutation of the n rows per epoch (int64, on the device), `lr=None` is the rate in force (the construction-time
 one, or the last one given), and the rollout head holds the new weights on return.
 
-HipLearner: the torch MlpPolicy's parameters live as VIEWS of one flat float32 buffer that the kernels update in place (so
+HipLearner: the torch MlpPolicy's (or, for a CNN head, CnnMlpPolicy's) parameters live as VIEWS of one flat float32 buffer that the kernels update in place (so
 state_dict(), save() / load() and deterministic_policy() see the learner's weights with no copy), and the rollout head is repacked
 from that buffer on the device after every update.  On the GPU (world size 1) a whole update -- every epoch's advantage moments,
 every minibatch step and the head repack -- is captured once per (batch buffers, minibatch size) into ONE hipGraph, a single linear
@@ -37,13 +37,15 @@ def _all_reduce_mean(flat, world, group):   # data-parallel PPO: one all-reduce 
 
 
 class HipLearner(object):
-    """PPO update of `policy` (MlpPolicy) for the rollout head `actor` (DeviceActor) through `lib`.  `graph`: capture the update
-    (GPU only).  `lr`: the rate in force until an update is given one."""
+    """PPO update of `policy` for the rollout head `actor` (DeviceActor) through `lib`: an MlpPolicy, or a CnnMlpPolicy when the
+    head is a CNN head (fwg_learner_create_cnn: the layout includes the conv; the parameter count below guards it).  `graph`:
+    capture the update (GPU only).  `lr`: the rate in force until an update is given one."""
 
     def __init__(self, lib, actor, policy, device, graph=True, betas=(0.9, 0.999), eps=1e-5, lr=2.5e-4):
         self._lib, self.actor, self.policy, self.device = lib, actor, policy, torch.device(device)
         h = ctypes.c_void_p()
-        nat.check(lib, lib.fwg_learner_create(actor._handle, ctypes.byref(h)))
+        create = lib.fwg_learner_create_cnn if actor.cnn else lib.fwg_learner_create
+        nat.check(lib, create(actor._handle, ctypes.byref(h)))
         self._h = h
         params = list(policy.parameters())
         self.num_params = int(lib.fwg_learner_num_params(h))
@@ -52,7 +54,7 @@ class HipLearner(object):
         with torch.no_grad():
             self.flat = torch.cat([p.detach().reshape(-1).float() for p in params]).to(self.device).contiguous()
             o = 0
-            for p in params:   # the module's parameters become views of the flat buffer (MlpPolicy.parameters() order)
+            for p in params:   # the module's parameters become views of the flat buffer (the policy's parameters() order)
                 p.data = self.flat[o:o + p.numel()].view_as(p)
                 o += p.numel()
         z = lambda *s, **k: torch.zeros(*s, device=self.device, **k)

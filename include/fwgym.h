@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FWG_ABI_VERSION 22
+#define FWG_ABI_VERSION 23
 
 #define FWG_N_VARS 23        /* simulator variables, see fwg_var */
 #define FWG_N_RESET_VARS 21  /* the keys of reset(state=...) records (fixed_wing.py:287,308; test-set format) */
@@ -511,6 +511,11 @@ int fwg_gae(int64_t n_steps, int64_t n_envs, const float* rewards, const float* 
  * precision).  Parameters, Adam moments and gradients are ONE flat float32 layout, MlpPolicy.parameters() order:
  *     log_std [act_dim] | pi.0.weight [64][obs_dim], pi.0.bias [64], pi.2.weight [64][64], pi.2.bias [64],
  *     pi.4.weight [act_dim][64], pi.4.bias [act_dim] | vf.0 ... vf.4 (output width 1)
+ * and for a CNN head (fwg_actor_set_conv: 5 x 12 window, 3 filters; fwg_learner_create_cnn), CnnMlpPolicy.parameters() order:
+ *     log_std [act_dim] | conv.weight [5][3], conv.bias [3] | pi.1.weight [64][36], pi.1.bias [64], pi.3.weight [64][64],
+ *     pi.3.bias [64], pi.5.weight [act_dim][64], pi.5.bias [act_dim] | vf.1 ... vf.5 (output width 1)
+ * (13 337 floats at act_dim 3).  The conv is one module shared by both networks: tanh(conv) of the normalised window, flattened
+ * feature-major, is their input, and its gradient sums both networks' terms.
  * -- fwg_learner_num_params() floats; a gradient buffer holds 4 more: the minibatch sums of the policy loss, the value loss,
  * 0.5 (logp - old logp)^2 and the clipped-ratio count.  Minibatch rows are gathered by index from the step-major rollout
  * buffers (fwg_rollout_step / fwg_actor_act outputs and fwg_gae's, flattened to [n_steps * n_envs]).  Every call takes
@@ -535,6 +540,10 @@ typedef struct fwg_ppo_batch {
 /* A learner for `head`'s networks (obs_dim, act_dim, device); it owns its partial-gradient scratch (~10 MB) and writes the
  * head's packed weights in fwg_actor_pack.  Destroy it before the head. */
 int fwg_learner_create(fwg_actor* head, fwg_learner** out);
+/* The same for a CNN head (one that fwg_actor_set_conv has given its conv): the layout includes the conv, the gradient passes
+ * through it, and fwg_actor_pack writes the conv's parameters too.  fwg_learner_create refuses a CNN head and this an MLP
+ * head; every other call below serves both kinds of learner.  Keep the head's kind while the learner lives. */
+int fwg_learner_create_cnn(fwg_actor* head, fwg_learner** out);
 void fwg_learner_destroy(fwg_learner* L);
 int64_t fwg_learner_num_params(const fwg_learner* L);
 /* Once per epoch: moments [n_minibatches][2] = mean and std (biased) + 1e-8 of adv over the rows

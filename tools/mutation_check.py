@@ -3,7 +3,8 @@
 a COPY of csrc/ (the fixes were commits b1ce333 and 8b54a4a, and round 6's log_plane fix), builds it, and runs the round-6 coverage
 tests against the mutant: every mutant must be caught ("What's weak" 2 / "Next round" 1).  The learner mutants
 (the PPO update, fwgym_learner.h) are plausible slips of a rewrite of its kernels; they run the emulated forms of
-tests/test_ppo_hip_contract.py.  The head mutants (head_*: the rollout head, fwgym_actor.h) likewise, against the emulated forms of
+tests/test_ppo_hip_contract.py (the ppo_cnn_* ones, slips in the backward pass through the CNN learner's conv, those of
+tests/test_ppo_hip_cnn.py).  The head mutants (head_*: the rollout head, fwgym_actor.h) likewise, against the emulated forms of
 tests/test_actor_contract.py; they are built for the host emulation only.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
@@ -58,6 +59,14 @@ MUTANTS = {
     "actor_pack_zero_low_parts": [
         ("fwgym_learner.h", "        frags[((net * 2 + 1) * nfw + f) * 64 + l] = frag_t{wl[0], wl[1], wl[2], wl[3]};",
          "        frags[((net * 2 + 1) * nfw + f) * 64 + l] = frag_t{0u, 0u, 0u, 0u};")],
+    # the CNN learner (k_ppo_grad<true>): the value network's term left out of dL / d(conv output) -- the conv is shared by pi and vf
+    "ppo_cnn_dc_drops_vf": [
+        ("fwgym_learner.h", "                ppo_mma_tile<CNN>(dc, Tb, LS, 1, tm0, 64, W1, FWG_CNN_K, 1, tn0, FWG_CNN_K, 64, 64, l);",
+         "                if (net == 0) ppo_mma_tile<CNN>(dc, Tb, LS, 1, tm0, 64, W1, FWG_CNN_K, 1, tn0, FWG_CNN_K, 64, 64, l);")],
+    # the conv's bias gradient summed over one of the 12 features only
+    "ppo_cnn_conv_bias_one_feature": [
+        ("fwgym_learner.h", "                    for (int j = 0; j < FWG_CNN_COLS; ++j)\n",
+         "                    for (int j = 0; j < (isw ? FWG_CNN_COLS : 1); ++j)\n")],
     # ---- the tag (configuration generation, episode) on prepared reset draws: what keeps a draw of the old ranges out after
     # set_curriculum_level.  The generation dropped from the two waves' decision whether a complete draw is used / installed
     "draw_ready_ignores_generation": [
@@ -109,7 +118,8 @@ _LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_con
 _CURRICULUM_TESTS = ["-k", "sparse or another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
 # the pytest arguments each mutant runs in `emu` mode
 _HEAD_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract.py")]
-TESTS = {name: (_LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+_CNN_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_cnn.py")]
+TESTS = {name: (_CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
