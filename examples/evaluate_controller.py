@@ -8,6 +8,7 @@ observation, as the reference's script does (evaluate_controller.py:118 there; t
     python examples/evaluate_controller.py --controller pid
     python examples/evaluate_controller.py --controller mlp --model tests/golden/mlp_controller.json
     python examples/evaluate_controller.py --controller cnn     (model: tests/golden/cnn_controller.npz)
+    python examples/evaluate_controller.py --controller cnn --device-loop     (the loop on the device; any controller)
 
 Test-set format: JSON list of {"state": {...}, "target": {...}} (converted from the reference's .npy test sets; the one
 under tests/golden/ is its examples/test_sets/test_set_wind_none_step20-20-3.npy)."""
@@ -31,10 +32,14 @@ def main():
                          "default tests/golden/mlp_controller.json / cnn_controller.npz")
     ap.add_argument("--turbulence", default="none", choices=["none", "light", "moderate", "severe"])
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--device-loop", action="store_true",
+                    help="run the protocol's loop on the device (evaluate.evaluate_on_set_device: no host read per step); same table")
     args = ap.parse_args()
     with open(args.test_set) as f:
         scenarios = json.load(f)
-    if args.controller == "pid":
+    if args.controller == "pid" and args.device_loop:
+        t = ev.evaluate_on_set_device(scenarios, presets.preset("examples"), turbulence_intensity=args.turbulence, device=args.device).table()
+    elif args.controller == "pid":
         res = ev.evaluate_on_set(scenarios, presets.preset("examples"), turbulence_intensity=args.turbulence, device=args.device)
     else:
         import numpy as np
@@ -50,10 +55,15 @@ def main():
         if "c1_w" in w:   # the first action of an episode: the same network on the raw observation (torch fp32)
             net = module_from_weights(w, np.asarray(m["obs_rms"]["mean"]).shape).to("cuda:{}".format(args.device))
             first = lambda obs: net.pi(obs.reshape(obs.shape[0], -1))
-        res = ev.evaluate_on_set(scenarios, presets.preset(args.controller), turbulence_intensity=args.turbulence, device=args.device,
-                                 policy=lambda obs: actor.act(obs.reshape(obs.shape[0], -1).contiguous(), deterministic=True)[1],
-                                 first_step_policy=first)
-    t = ev.summarize(res)
+        if args.device_loop:
+            t = ev.evaluate_on_set_device(scenarios, presets.preset(args.controller), controller=actor, turbulence_intensity=args.turbulence,
+                                          device=args.device, first_step_policy=first).table()
+        else:
+            res = ev.evaluate_on_set(scenarios, presets.preset(args.controller), turbulence_intensity=args.turbulence, device=args.device,
+                                     policy=lambda obs: actor.act(obs.reshape(obs.shape[0], -1).contiguous(), deterministic=True)[1],
+                                     first_step_policy=first)
+    if not args.device_loop:
+        t = ev.summarize(res)
     print("controller {}, {} scenarios, turbulence {}".format(args.controller, len(scenarios), args.turbulence))
     print("success %      roll {roll:6.1f}  pitch {pitch:6.1f}  Va {Va:6.1f}  all {all:6.1f}".format(**t["success_%"]))
     for k, unit in (("rise_time", "s"), ("settling_time", "s"), ("overshoot", "%")):

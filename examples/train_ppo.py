@@ -32,10 +32,18 @@ from gym_fixed_wing.rollout import CnnMlpPolicy  # noqa: E402
 
 
 def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, learning_rate=5e-4, n_steps=128, curriculum=True,
-          config=None, log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch", policy="mlp"):
+          config=None, log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch", policy="mlp",
+          test_set=None, test_turbulence="none"):
     """policy: "mlp" (MlpPolicy on the examples config's 12-vector) or "cnn" (CnnMlpPolicy on the cnn config's 5 x 12 matrix
     observations: the reference's --policy CNN, train_rl_controller.py:179-197).  update: "torch" or "hip" (for the cnn policy
-    "hip" is PPO's "hip_cnn").  config: preset name, default by policy."""
+    "hip" is PPO's "hip_cnn").  config: preset name, default by policy.
+    test_set: a list of scenarios (or the path of one as JSON, the format of examples/evaluate_controller.py): rank 0 flies it
+    with the current policy whenever num_timesteps crosses a fifth of `timesteps` -- the reference's test_interval =
+    training_steps / 5 (train_rl_controller.py --test-set-path), four evaluations in a run -- by PPO.evaluate (the evaluation
+    protocol on the device); the table goes into that update's info["test"]."""
+    if isinstance(test_set, str):
+        with open(test_set) as f:
+            test_set = json.load(f)
     config = config or ("cnn" if policy == "cnn" else "examples")
     # (the cnn configuration's build-time kernel instance is the shipped one, derived views on: presets.SPECIALISED ship_cnn_log)
     vec = make_sharded_env(presets.preset(config), total_envs=envs, rank=rank, world_size=world, device=local,
@@ -53,8 +61,18 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
               learning_rate=learning_rate, fused=fused, ent_coef=ent_coef, update=update)
     t0 = time.perf_counter()
     window = []    # success over the last finished episodes (the reference's ep_info_buf holds the last 100)
+    tests_done = [0]
 
     def on_info(info):
+        fifth = int(info["timesteps"] // (timesteps / 5.0))
+        if test_set is not None and rank == 0 and min(fifth, 4) > tests_done[0]:
+            tests_done[0] = min(fifth, 4)
+            info["test"] = ppo.evaluate(test_set, turbulence_intensity=test_turbulence)
+            if log is not None:
+                t = info["test"]
+                log("update {:4d}  test set ({} scenarios, turbulence {}): success_all {:.1f} %  settling {}  control variation {:.3f}".format(
+                    info["update"], len(test_set), test_turbulence, t["success_%"]["all"],
+                    " ".join("{} {:.2f} s".format(k, v) for k, v in t["settling_time"].items()), t["control_variation"]["all"]))
         if info["episodes"] > 0:
             window.append((info["episodes"], info["success"]["all"], info["level"]))
         if rank == 0 and log is not None and (info["episodes"] > 0 or info["update"] % 20 == 0):
@@ -84,6 +102,8 @@ def main():
     ap.add_argument("--update", choices=("torch", "hip"), default="torch", help="PPO update: torch autograd (default) or the HIP kernels")
     ap.add_argument("--policy", choices=("mlp", "cnn"), default="mlp",
                     help="mlp: MlpPolicy, examples config; cnn: CnnMlpPolicy (3 filters), cnn config (either update)")
+    ap.add_argument("--test-set", default=None, help="scenarios (JSON) flown with the current policy at every fifth of --timesteps (rank 0)")
+    ap.add_argument("--test-turbulence", default="none", choices=["none", "light", "moderate", "severe"])
     ap.add_argument("--out", default=None, help="save weights + VecNormalize statistics (.npz)")
     ap.add_argument("--curve", default=None, help="write the learning curve (JSON)")
     args = ap.parse_args()
@@ -93,7 +113,8 @@ def main():
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local))
     torch.cuda.set_device(local)
     ppo, res = train(args.envs, args.timesteps, args.seed, args.nminibatches, args.noptepochs, args.lr, curriculum=not args.disable_curriculum,
-                     rank=rank, world=world, local=local, ent_coef=args.ent_coef, update=args.update, policy=args.policy)
+                     rank=rank, world=world, local=local, ent_coef=args.ent_coef, update=args.update, policy=args.policy,
+                     test_set=args.test_set, test_turbulence=args.test_turbulence)
     if rank == 0:
         print("{:.3e} env-steps in {:.1f} s = {:.3e} env-steps/s INCLUDING the optimiser ({} updates)".format(
             ppo.num_timesteps, res["seconds"], res["env_steps_per_s"], res["updates"]))

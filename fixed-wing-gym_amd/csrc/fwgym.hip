@@ -19,6 +19,7 @@
 #include "fwgym_env.h"
 #include "fwgym_actor.h"   // the rollout head (k_rollout below runs it in the same launch as the env step)
 #include "fwgym_learner.h" // the PPO update on the device (fwg_ppo_*)
+#include "fwgym_eval.h"    // the evaluation protocol on the device (fwg_pid_act, fwg_eval_advance)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
@@ -2272,6 +2273,40 @@ int fwg_gae(int64_t n_steps, int64_t n_envs, const float* rewards, const float* 
     if (n_steps < 1 || n_envs < 1) return fail_with(FWG_ERR_INVALID, "fwg_gae: n_steps and n_envs must be positive");
     hipLaunchKernelGGL(k_gae, dim3((unsigned)((n_envs + 63) / 64)), dim3(256), 4 * 64 * 2 * sizeof(float), (hipStream_t)stream, rewards, values, dones, last_value,
                        gamma, lam, adv_out, ret_out, (long)n_steps, (long)n_envs);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_pid_act(int64_t n_envs, const float* obs, int obs_stride, const int32_t* obs_cols_host, const float* target, int target_stride,
+                const int32_t* target_cols_host, fwg_pid_gains gains, float* integrators, float* actions_out, void* stream) {
+    if (!obs || !obs_cols_host || !target || !target_cols_host || !integrators || !actions_out)
+        return fail_with(FWG_ERR_INVALID, "fwg_pid_act: null argument");
+    if (n_envs < 1) return fail_with(FWG_ERR_INVALID, "fwg_pid_act: n_envs must be positive");
+    for (int i = 0; i < 6; ++i)
+        if (obs_cols_host[i] < 0 || obs_cols_host[i] >= obs_stride)
+            return fail_with(FWG_ERR_INVALID, "fwg_pid_act: observation column " + std::to_string(obs_cols_host[i]) + " outside a row of " + std::to_string(obs_stride));
+    for (int i = 0; i < 3; ++i)
+        if (target_cols_host[i] < 0 || target_cols_host[i] >= target_stride)
+            return fail_with(FWG_ERR_INVALID, "fwg_pid_act: target column " + std::to_string(target_cols_host[i]) + " outside a row of " + std::to_string(target_stride));
+    const PidCols c = {obs_cols_host[0], obs_cols_host[1], obs_cols_host[2], obs_cols_host[3], obs_cols_host[4], obs_cols_host[5],
+                       target_cols_host[0], target_cols_host[1], target_cols_host[2]};
+    hipLaunchKernelGGL(k_pid_act, dim3((unsigned)((n_envs + FWG_EVAL_THREADS - 1) / FWG_EVAL_THREADS)), dim3(FWG_EVAL_THREADS), 0, (hipStream_t)stream,
+                       (long)n_envs, obs, obs_stride, target, target_stride, c, gains, integrators, actions_out);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_eval_advance(int64_t n_envs, int64_t t, const float* reward, const uint8_t* done, const uint8_t* term_code, const float* metrics,
+                     uint8_t* active, int32_t* length, uint8_t* termination, float* metrics_final, float* reward_trace, int64_t trace_steps,
+                     float* actions_io, void* stream) {
+    if (!active || !length || !termination || !metrics_final) return fail_with(FWG_ERR_INVALID, "fwg_eval_advance: null argument");
+    if (n_envs < 1) return fail_with(FWG_ERR_INVALID, "fwg_eval_advance: n_envs must be positive");
+    if (t < 0 || t > 0x7fffffff) return fail_with(FWG_ERR_INVALID, "fwg_eval_advance: t must be a step count (0 .. 2^31 - 1)");
+    if (t > 0 && (!reward || !done || !term_code || !metrics))
+        return fail_with(FWG_ERR_INVALID, "fwg_eval_advance: null argument (the results of step t - 1 are folded when t > 0)");
+    if (reward_trace && t > trace_steps) return fail_with(FWG_ERR_INVALID, "fwg_eval_advance: step t - 1 lies beyond the trace's rows");
+    hipLaunchKernelGGL(k_eval_advance, dim3((unsigned)((n_envs + FWG_EVAL_THREADS - 1) / FWG_EVAL_THREADS)), dim3(FWG_EVAL_THREADS), 0, (hipStream_t)stream,
+                       (long)n_envs, (long)t, reward, done, term_code, metrics, active, length, termination, metrics_final, reward_trace, actions_io);
     HIP_TRY(hipGetLastError());
     return FWG_OK;
 }

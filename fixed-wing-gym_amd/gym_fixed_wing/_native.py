@@ -3,7 +3,7 @@ module without a built library raises, there is no CPU fallback."""
 import ctypes as C
 import os
 
-FWG_ABI_VERSION = 23
+FWG_ABI_VERSION = 24
 N_VARS = 23
 N_RESET_VARS = 21
 N_PARAMS = 49
@@ -149,6 +149,13 @@ class PpoBatch(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ["obs", "actions", "values", "logp", "adv", "returns"]]
 
 
+class PidGains(C.Structure):
+    """fwg_pid_gains: gains, output limits (radians / throttle fraction) and time step of the PID baseline, passed by value."""
+    _fields_ = [(n, C.c_float) for n in
+                ["k_p_phi", "k_i_phi", "k_d_phi", "k_p_theta", "k_i_theta", "k_d_theta", "k_p_V", "k_i_V",
+                 "delta_e_min", "delta_e_max", "delta_a_min", "delta_a_max", "delta_t_min", "delta_t_max", "dt", "pad_"]]
+
+
 PPO_NSTAT = 4   # loss sums appended to a gradient buffer (include/fwgym.h "PPO update")
 
 
@@ -194,6 +201,8 @@ PROTOTYPES = {
     "fwg_obs_window": (_int, [_vp, C.POINTER(_i64)]),
     "fwg_obs_gather": (_int, [_vp] * 4),
     "fwg_gae": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp]),
+    "fwg_pid_act": (_int, [_i64, _vp, _int, C.POINTER(C.c_int32), _vp, _int, C.POINTER(C.c_int32), PidGains, _vp, _vp, _vp]),
+    "fwg_eval_advance": (_int, [_i64, _i64] + [_vp] * 9 + [_i64, _vp, _vp]),
     "fwg_selftest_philox": (_int, [_vp, _vp, _i64, _vp]),
     "fwg_actor_create": (_int, [_int, _i64, _int, _int, _f32, _f32, _f32, _f32, C.POINTER(_vp)]),
     "fwg_actor_destroy": (None, [_vp]),

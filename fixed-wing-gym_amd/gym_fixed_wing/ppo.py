@@ -177,6 +177,45 @@ class PPO(object):
             return pi(((x.reshape(x.shape[0], -1) - mean) / std).clamp(-10.0, 10.0))
         return act
 
+    def evaluate(self, scenarios, turbulence_intensity="none", first_step="raw", config=None):
+        """The current policy on a test set, by the evaluation protocol on the device (evaluate.evaluate_on_set_device: what the
+        reference's training script does at every fifth of a run, train_rl_controller.py --test-set-path) -> the table of
+        evaluate.summarize().  One evaluation env (auto_reset off, the evaluation overrides on `config`, default: the training
+        env's configuration) and one DeviceActor(training=False) are kept per scenario set; each call loads the current weights
+        and the training head's statistics into that head and flies the set.  first_step: "raw" = the reference's protocol, the
+        first action of every episode comes from the policy network on the UN-normalised reset observation
+        (evaluate_controller.py:118); "normalised" = the head acts on every step.  Touches neither the training env nor the
+        training head, and draws no random number."""
+        import copy
+        import hashlib
+        import json
+        from .actor import DeviceActor
+        from .evaluate import DeviceEvaluation, evaluation_overrides
+        from .vec_env import FixedWingVecEnv
+        if first_step not in ("raw", "normalised"):
+            raise ValueError("first_step must be 'raw' or 'normalised', not {!r}".format(first_step))
+        key = hashlib.sha256(json.dumps([scenarios, turbulence_intensity, config if config is None or isinstance(config, (str, dict)) else str(config)],
+                                        sort_keys=True).encode()).hexdigest()
+        cache = self.__dict__.setdefault("_eval", {})
+        if key not in cache:
+            sim_kw = {"turbulence": turbulence_intensity != "none", "turbulence_intensity": turbulence_intensity}
+            vec = FixedWingVecEnv(copy.deepcopy(self.vec.cfg) if config is None else config, num_envs=len(scenarios),
+                                  config_kw=evaluation_overrides(False), sim_config_kw=sim_kw, auto_reset=False, seed=self.vec._seed,
+                                  _backend=self.vec._mem)
+            head = DeviceActor.for_env(vec, training=False, gamma=self.hp["gamma"], precise=self.actor.precise)
+            cache[key] = (vec, head, DeviceEvaluation(vec, head, rewards=False))
+        vec, head, run = cache[key]
+        head.load_policy(self.policy)
+        st = self.actor.get_stats()
+        head.set_stats(st["obs_mean"], st["obs_var"], st["obs_count"], st["ret_mean"], st["ret_var"], st["ret_count"])
+        first = None
+        if first_step == "raw":
+            first = lambda obs: self.policy.pi(torch.as_tensor(obs).reshape(len(scenarios), -1))
+        vec.seed(self.vec._seed)      # (the same turbulence realisation at every call: evaluations of one run are comparable)
+        run.reset(scenarios, first)
+        run.run()
+        return run.result().table(vec.dt)
+
     def save(self, path):
         """Weights + VecNormalize statistics (the reference's save_model: model.pkl + save_running_average)."""
         st = self.actor.get_stats()

@@ -437,15 +437,18 @@ class FixedWingVecEnv(object):
         self.step_async(actions)
         return self.step_wait()
 
-    def step_device(self, actions, want_obs=True):
+    def step_device(self, actions, want_obs=True, target_out=False):
         """Fast path for on-device rollouts: no info objects; returns the (obs, reward, done) device tensors.
         `actions`: float32, contiguous, [N, 3], on this env's device.  want_obs=False (row-log mode): the caller reads
-        the observation out of the log itself (the HIP rollout head does, fwg_actor_set_obs_log), so no view/gather."""
+        the observation out of the log itself (the HIP rollout head does, fwg_actor_set_obs_log), so no view/gather.
+        target_out=True: the step also writes info["target"] into self._target, as step() does (the device evaluation loop:
+        the PID baseline follows it)."""
         m = self._mem
         actions = self._checked_actions(actions)
         nat.check(self._lib, self._lib.fwg_step(self._handle, m.ptr(actions), m.ptr(self._obs_buf), m.ptr(self._rew), m.ptr(self._done),
                                                 m.ptr(self._term), m.ptr(self._term_obs), m.ptr(self._metrics),
-                                                ctypes.c_void_p(), m.stream()))   # targets stay in the state arena
+                                                m.ptr(self._target) if target_out else ctypes.c_void_p(),   # (default: targets stay in the state arena)
+                                                m.stream()))
         if want_obs:
             self._refresh_obs_view()
         return self._obs, self._rew, self._done

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FWG_ABI_VERSION 23
+#define FWG_ABI_VERSION 24
 
 #define FWG_N_VARS 23        /* simulator variables, see fwg_var */
 #define FWG_N_RESET_VARS 21  /* the keys of reset(state=...) records (fixed_wing.py:287,308; test-set format) */
@@ -565,6 +565,63 @@ int fwg_ppo_step(fwg_learner* L, const fwg_ppo_batch* b, const int64_t* idx, int
 /* The head's weights from the flat parameters, on the device: what fwg_actor_set_weights does from host arrays, with no host
  * round trip (a captured rollout sees the new weights at its next replay). */
 int fwg_actor_pack(fwg_learner* L, const float* params, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Evaluation: the reference's evaluate_model_on_set (examples/evaluate_controller.py:44-169) without a host read per step.
+ * Every scenario of a test set flies in its own env (fwg_config.auto_reset = 0) to its FIRST episode end; from then on the env
+ * is fed zero actions and keeps stepping -- and keeps reporting done -- until the last scenario has ended.  Per step t:
+ *     controller (fwg_pid_act, or fwg_actor_act with deterministic = 1 and frozen statistics) -> actions
+ *     fwg_finish_episodes(env, metrics)      the metrics columns of the envs step t - 1 reported done
+ *     fwg_eval_advance(t, ...)               folds step t - 1, zeroes the actions of finished envs
+ *     fwg_step(env, actions, ..., target_out)
+ * and after the last step one fwg_finish_episodes + fwg_eval_advance with actions_io = NULL.  Both calls below are stateless:
+ * one launch on `stream` over caller-owned device buffers, no allocation, no synchronisation (as fwg_gae).
+ * ------------------------------------------------------------------------------------------------------------------ */
+
+/* Gains, output limits and time step of the PID baseline (pyfly.pid_controller.PIDController; the reference builds it at
+ * fixed_wing.py:1281-1300 and examples/evaluate_controller.py:82-84), passed from the host BY VALUE.  Defaults of
+ * gym_fixed_wing.pid.BatchedPID: k_p_phi 1, k_i_phi 0, k_d_phi 0.5 | k_p_theta -4, k_i_theta -0.75, k_d_theta -0.1 | k_p_V 0.5,
+ * k_i_V 0.1 | elevator -30 .. 35 deg, aileron -30 .. 30 deg (radians here), throttle 0 .. 1 | dt 0.01. */
+typedef struct fwg_pid_gains {
+    float k_p_phi, k_i_phi, k_d_phi;
+    float k_p_theta, k_i_theta, k_d_theta;
+    float k_p_V, k_i_V;
+    float delta_e_min, delta_e_max, delta_a_min, delta_a_max, delta_t_min, delta_t_max;
+    float dt;
+    float pad_;
+} fwg_pid_gains;
+
+/* PIDController.get_action for n_envs aircraft (examples/evaluate_controller.py:120-124,143-150).
+ *   obs              : float32 [N][obs_stride], a dense observation batch (or one plane of the row log, obs_stride = n_obs)
+ *   obs_cols_host    : 6 column indices into a row: roll, pitch, Va, omega_p, omega_q, omega_r (each < obs_stride)
+ *   target           : float32 [N][target_stride], what fwg_step writes through target_out (info["target"])
+ *   target_cols_host : 3 column indices into a row: roll, pitch, Va (each < target_stride)
+ *   integrators      : float32 [3][N] IN-OUT, rows roll, pitch, Va; zero them to reset the controller
+ *   actions_out      : float32 [N][3] elevator, aileron, throttle, clipped to the limits
+ * aileron = -k_p_phi e_phi - k_i_phi I_phi - k_d_phi p, elevator = -k_p_theta e_theta - k_i_theta I_theta - k_d_theta (q cos phi
+ * - r sin phi), throttle = -k_p_V e_Va - k_i_V I_Va with e = state - target: computed from the integrals as they stand, THEN
+ * I += dt e.  A NaN input gives a NaN action (the limits do not hide it). */
+int fwg_pid_act(int64_t n_envs, const float* obs, int obs_stride, const int32_t* obs_cols_host, const float* target, int target_stride,
+                const int32_t* target_cols_host, fwg_pid_gains gains, float* integrators, float* actions_out, void* stream);
+
+/* The episode tracker: call it once per step t = 0, 1, ... after the controller and before fwg_step, with the reward_out /
+ * done_out / term_code_out of step t - 1 and the metrics block fwg_finish_episodes has just written (all four may be NULL at
+ * t == 0, where nothing is folded).  IN-OUT, initialised by the caller before t = 0:
+ *   active        : uint8 [N]   1 while the scenario's first episode is running
+ *   length        : int32 [N]   steps of that episode so far
+ *   termination   : uint8 [N]   FWG_TERM_* of the FIRST episode end (FWG_TERM_NONE while running)
+ *   metrics_final : float32 [FWG_N_METRICS][N]  the metrics column of the FIRST episode end (untouched while running)
+ *   reward_trace  : NULL or float32 [trace_steps][N]; row t - 1 is written for EVERY env: the reward where the env was active
+ *                   during step t - 1, NaN where it was not -- every cell exactly once, so the buffer needs no initialisation
+ *   actions_io    : NULL or float32 [N][3]; the rows of inactive envs are overwritten with zeros (stored, not multiplied: a NaN
+ *                   from the policy of a finished, tumbling aircraft never reaches the step)
+ * Per active env: trace[t - 1] = reward, length = t, and where done: termination = term_code, metrics_final[:] = metrics[:],
+ * active = 0.  A done an env reports AFTER its first end changes nothing.  The gate sees the `active` this call leaves.
+ * The last call (after the final step) passes actions_io = NULL.  Refused (FWG_ERR_INVALID): t < 0, t > trace_steps with a
+ * trace, n_envs <= 0, null buffers. */
+int fwg_eval_advance(int64_t n_envs, int64_t t, const float* reward, const uint8_t* done, const uint8_t* term_code, const float* metrics,
+                     uint8_t* active, int32_t* length, uint8_t* termination, float* metrics_final, float* reward_trace, int64_t trace_steps,
+                     float* actions_io, void* stream);
 
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);

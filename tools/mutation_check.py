@@ -5,7 +5,8 @@ tests against the mutant: every mutant must be caught ("What's 
 (the PPO update, fwgym_learner.h) are plausible slips of a rewrite of its kernels; they run the emulated forms of
 tests/test_ppo_hip_contract.py (the ppo_cnn_* ones, slips in the backward pass through the CNN learner's conv, those of
 tests/test_ppo_hip_cnn.py).  The head mutants (head_*: the rollout head, fwgym_actor.h) likewise, against the emulated forms of
-tests/test_actor_contract.py; they are built for the host emulation only.
+tests/test_actor_contract.py; they are built for the host emulation only.  The eval_* mutants (the evaluation protocol on the device,
+fwgym_eval.h) run tests/test_eval_device.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
@@ -110,6 +111,21 @@ MUTANTS = {
     # the act counter (the noise stream's counter, and the rotation of the accumulator sets) kept by deterministic acts
     "head_counter_skips_deterministic_acts": [
         ("fwgym_actor.h", "                S1.act_counter = act_ctr + 1u;", "                S1.act_counter = act_ctr + (A.deterministic ? 0u : 1u);")],
+    # ---- the evaluation protocol on the device (fwgym_eval.h); they run the emulated forms, tests/test_eval_device.py.
+    # The tracker latches every done, not the first: metrics_final and termination overwritten when a finished env reports done again
+    "eval_tracker_latches_every_done": [
+        ("fwgym_eval.h", "    if (t > 0) {\n        if (on) {\n", "    if (t > 0) {\n        if (!on && done[e]) {\n"
+         "            termination[e] = term[e];\n            for (int k = 0; k < FWG_N_METRICS; ++k) metrics_final[k * N + e] = metrics[k * N + e];\n        }\n        if (on) {\n")],
+    # the gate multiplies the action rows of finished envs by zero instead of storing zeros (0 * NaN = NaN reaches the step)
+    "eval_gate_multiplies": [
+        ("fwgym_eval.h", "{ actions[3 * e] = 0.f; actions[3 * e + 1] = 0.f; actions[3 * e + 2] = 0.f; }",
+         "{ actions[3 * e] *= 0.f; actions[3 * e + 1] *= 0.f; actions[3 * e + 2] *= 0.f; }")],
+    # the PID adds dt * e to the integrators BEFORE it computes the action
+    "eval_pid_integrates_first": [
+        ("fwgym_eval.h", "    const float i_phi = integ[e], i_theta = integ[N + e], i_va = integ[2 * N + e];",
+         "    const float i_phi = integ[e] + g.dt * e_phi, i_theta = integ[N + e] + g.dt * e_theta, i_va = integ[2 * N + e] + g.dt * e_va;"),
+        ("fwgym_eval.h", "    integ[e] = i_phi + g.dt * e_phi;\n    integ[N + e] = i_theta + g.dt * e_theta;\n    integ[2 * N + e] = i_va + g.dt * e_va;\n",
+         "    integ[e] = i_phi;\n    integ[N + e] = i_theta;\n    integ[2 * N + e] = i_va;\n")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -119,7 +135,8 @@ _CURRICULUM_TESTS = ["-k", "sparse or another_seed", os.path.join(ROOT, "tests",
 # the pytest arguments each mutant runs in `emu` mode
 _HEAD_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract.py")]
 _CNN_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_cnn.py")]
-TESTS = {name: (_CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+_EVAL_TESTS = [os.path.join(ROOT, "tests", "test_eval_device.py")]
+TESTS = {name: (_EVAL_TESTS if name.startswith("eval_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
