@@ -1,6 +1,9 @@
 """The CNN controller on the MI355X: the HIP head's conv front end (k_actor_act_cnn) against torch fp32 CnnMlpPolicy at 65 536
 envs of the cnn preset (row log read in place and the dense batch), the shipped controller (tests/golden/cnn_controller.npz)
-flying the 100 shipped no-wind scenarios through the reference's evaluation protocol, and a short PPO run from scratch."""
+flying the 100 shipped no-wind scenarios through the reference's evaluation protocol, and a short PPO run from scratch.
+This file keeps the large batch and the closed loop; the head's arithmetic per element against float64 -- tile tails, act_dim 1..4,
+the single-product instance, the row log across wraps, clipping, the noise stream, capture -- is pinned by
+tests/test_actor_contract_cnn.py."""
 import json
 import os
 import time

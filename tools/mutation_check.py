@@ -5,7 +5,8 @@ tests against the mutant: every mutant must be caught ("What's 
 (the PPO update, fwgym_learner.h) are plausible slips of a rewrite of its kernels; they run the emulated forms of
 tests/test_ppo_hip_contract.py (the ppo_cnn_* ones, slips in the backward pass through the CNN learner's conv, those of
 tests/test_ppo_hip_cnn.py).  The head mutants (head_*: the rollout head, fwgym_actor.h) likewise, against the emulated forms of
-tests/test_actor_contract.py; they are built for the host emulation only.  The eval_* mutants (the evaluation protocol on the device,
+tests/test_actor_contract.py (the head_cnn_* ones, slips in the CNN head's own code, those of tests/test_actor_contract_cnn.py); they are
+built for the host emulation only.  The eval_* mutants (the evaluation protocol on the device,
 fwgym_eval.h) run tests/test_eval_device.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
@@ -111,6 +112,25 @@ MUTANTS = {
     # the act counter (the noise stream's counter, and the rotation of the accumulator sets) kept by deterministic acts
     "head_counter_skips_deterministic_acts": [
         ("fwgym_actor.h", "                S1.act_counter = act_ctr + 1u;", "                S1.act_counter = act_ctr + (A.deterministic ? 0u : 1u);")],
+    # ---- the CNN rollout head (actor_block<SPLIT, 3, true> and its launch), arithmetic only and in bounds; they run the emulated
+    # forms of tests/test_actor_contract_cnn.py.  Every filter's conv output takes filter 0's bias
+    "head_cnn_bias_of_filter_0": [
+        ("fwgym_actor.h", "            float z = cnn_p[FWG_CNN_ROWS * FWG_CNN_FILTERS + c];", "            float z = cnn_p[FWG_CNN_ROWS * FWG_CNN_FILTERS + 0];")],
+    # the conv without the window's last row (the newest record)
+    "head_cnn_conv_drops_last_row": [
+        ("fwgym_actor.h", "for (int r = 0; r < FWG_CNN_ROWS; ++r) z = fmaf(", "for (int r = 0; r < FWG_CNN_ROWS - 1; ++r) z = fmaf(")],
+    # the CNN branch's own normalisation line without the clip
+    "head_cnn_no_obs_clip": [
+        ("fwgym_actor.h", "xn[4 * q + i] = fminf(fmaxf((r4[i] - mean_s[4 * q + i]) * rstd_s[4 * q + i], -A.clip_obs), A.clip_obs);",
+         "xn[4 * q + i] = (r4[i] - mean_s[4 * q + i]) * rstd_s[4 * q + i];")],
+    # precise=False launches the split-bf16 instance all the same (its LDS request is the larger one: in bounds)
+    "head_cnn_plain_launches_split": [
+        ("fwgym.hip", "        if (a->precise) hipLaunchKernelGGL((k_actor_act_cnn<3>), grid, block, a->lds_cnn[1], st, A);\n"
+                      "        else hipLaunchKernelGGL((k_actor_act_cnn<1>), grid, block, a->lds_cnn[0], st, A);\n",
+         "        hipLaunchKernelGGL((k_actor_act_cnn<3>), grid, block, a->lds_cnn[1], st, A);\n")],
+    # on a row log every row of the window read from the window's first plane (the dense batch is read as before)
+    "head_cnn_log_window_one_plane": [
+        ("fwgym_actor.h", "    return A.obs + ((win + r) * A.N + e) * A.obs_n + j;", "    return A.obs + (win * A.N + e) * A.obs_n + j;")],
     # ---- the evaluation protocol on the device (fwgym_eval.h); they run the emulated forms, tests/test_eval_device.py.
     # The tracker latches every done, not the first: metrics_final and termination overwritten when a finished env reports done again
     "eval_tracker_latches_every_done": [
@@ -136,7 +156,8 @@ _CURRICULUM_TESTS = ["-k", "sparse or another_seed", os.path.join(ROOT, "tests",
 _HEAD_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract.py")]
 _CNN_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_cnn.py")]
 _EVAL_TESTS = [os.path.join(ROOT, "tests", "test_eval_device.py")]
-TESTS = {name: (_EVAL_TESTS if name.startswith("eval_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+_HEAD_CNN_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract_cnn.py")]
+TESTS = {name: (_EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
