@@ -33,14 +33,17 @@ from gym_fixed_wing.rollout import CnnMlpPolicy  # noqa: E402
 
 def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, learning_rate=5e-4, n_steps=128, curriculum=True,
           config=None, log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch", policy="mlp",
-          test_set=None, test_turbulence="none"):
+          test_set=None, test_turbulence="none", render_dir=None, render_every=600.0):
     """policy: "mlp" (MlpPolicy on the examples config's 12-vector) or "cnn" (CnnMlpPolicy on the cnn config's 5 x 12 matrix
     observations: the reference's --policy CNN, train_rl_controller.py:179-197).  update: "torch" or "hip" (for the cnn policy
     "hip" is PPO's "hip_cnn").  config: preset name, default by policy.
     test_set: a list of scenarios (or the path of one as JSON, the format of examples/evaluate_controller.py): rank 0 flies it
     with the current policy whenever num_timesteps crosses a fifth of `timesteps` -- the reference's test_interval =
     training_steps / 5 (train_rl_controller.py --test-set-path), four evaluations in a run -- by PPO.evaluate (the evaluation
-    protocol on the device); the table goes into that update's info["test"]."""
+    protocol on the device); the table goes into that update's info["test"].
+    render_dir: rank 0 records env 0 on the device (gym_fixed_wing.recorder.FlightRecorder) and, whenever `render_every` seconds
+    have passed and env 0 has finished another episode, saves that episode's figure as <render_dir>/<num_timesteps>.png -- the
+    reference's render_interval = 600 s of training episodes (train_rl_controller.py:95-104)."""
     if isinstance(test_set, str):
         with open(test_set) as f:
             test_set = json.load(f)
@@ -48,6 +51,12 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
     # (the cnn configuration's build-time kernel instance is the shipped one, derived views on: presets.SPECIALISED ship_cnn_log)
     vec = make_sharded_env(presets.preset(config), total_envs=envs, rank=rank, world_size=world, device=local,
                            derived_views=config == "cnn", seed=seed)
+    recorder = None
+    if render_dir is not None and rank == 0:
+        # before the first reset (an episode is recorded from its reset on) and before PPO captures its rollout (a graph captured
+        # earlier would replay without the recorder's launches)
+        from gym_fixed_wing.recorder import FlightRecorder
+        recorder = FlightRecorder(vec, env_ids=(0,))
     sched = CurriculumSchedule(level=0.25 if curriculum else 1.0)     # (train_rl_controller.py:162: curriculum_level = 0.25)
     vec.set_curriculum_level(sched.level)
     vec.reset()
@@ -62,8 +71,18 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
     t0 = time.perf_counter()
     window = []    # success over the last finished episodes (the reference's ep_info_buf holds the last 100)
     tests_done = [0]
+    rendered = {"at": t0, "episodes": 0, "files": []}
 
     def on_info(info):
+        if recorder is not None and time.perf_counter() - rendered["at"] >= render_every:
+            n_done = recorder.completed(0)
+            if n_done > rendered["episodes"]:
+                path = os.path.join(render_dir, "{}.png".format(int(info["timesteps"])))
+                recorder.render(mode="plot", show=False, save_path=path)
+                rendered.update(at=time.perf_counter(), episodes=n_done)
+                rendered["files"].append(path)
+                if log is not None:
+                    log("update {:4d}  rendered episode {} of env 0 -> {}".format(info["update"], n_done, path))
         fifth = int(info["timesteps"] // (timesteps / 5.0))
         if test_set is not None and rank == 0 and min(fifth, 4) > tests_done[0]:
             tests_done[0] = min(fifth, 4)
@@ -86,7 +105,8 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
     ppo.learn(timesteps, log=on_info)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return ppo, {"seconds": dt, "env_steps_per_s": ppo.num_timesteps / dt, "updates": ppo.updates, "episodes_log": window}
+    return ppo, {"seconds": dt, "env_steps_per_s": ppo.num_timesteps / dt, "updates": ppo.updates, "episodes_log": window,
+                 "rendered": rendered["files"]}
 
 
 def main():
@@ -104,6 +124,8 @@ def main():
                     help="mlp: MlpPolicy, examples config; cnn: CnnMlpPolicy (3 filters), cnn config (either update)")
     ap.add_argument("--test-set", default=None, help="scenarios (JSON) flown with the current policy at every fifth of --timesteps (rank 0)")
     ap.add_argument("--test-turbulence", default="none", choices=["none", "light", "moderate", "severe"])
+    ap.add_argument("--render-dir", default=None, help="save the figure of a training episode of env 0 as DIR/<num_timesteps>.png (rank 0)")
+    ap.add_argument("--render-every", type=float, default=600.0, help="seconds between two rendered episodes (the reference's interval)")
     ap.add_argument("--out", default=None, help="save weights + VecNormalize statistics (.npz)")
     ap.add_argument("--curve", default=None, help="write the learning curve (JSON)")
     args = ap.parse_args()
@@ -114,7 +136,8 @@ def main():
     torch.cuda.set_device(local)
     ppo, res = train(args.envs, args.timesteps, args.seed, args.nminibatches, args.noptepochs, args.lr, curriculum=not args.disable_curriculum,
                      rank=rank, world=world, local=local, ent_coef=args.ent_coef, update=args.update, policy=args.policy,
-                     test_set=args.test_set, test_turbulence=args.test_turbulence)
+                     test_set=args.test_set, test_turbulence=args.test_turbulence, render_dir=args.render_dir,
+                     render_every=args.render_every)
     if rank == 0:
         print("{:.3e} env-steps in {:.1f} s = {:.3e} env-steps/s INCLUDING the optimiser ({} updates)".format(
             ppo.num_timesteps, res["seconds"], res["env_steps_per_s"], res["updates"]))

@@ -20,6 +20,7 @@
 #include "fwgym_actor.h"   // the rollout head (k_rollout below runs it in the same launch as the env step)
 #include "fwgym_learner.h" // the PPO update on the device (fwg_ppo_*)
 #include "fwgym_eval.h"    // the evaluation protocol on the device (fwg_pid_act, fwg_eval_advance)
+#include "fwgym_record.h"  // the device flight recorder (fwg_record_start, fwg_record)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
@@ -2307,6 +2308,39 @@ int fwg_eval_advance(int64_t n_envs, int64_t t, const float* reward, const uint8
     if (reward_trace && t > trace_steps) return fail_with(FWG_ERR_INVALID, "fwg_eval_advance: step t - 1 lies beyond the trace's rows");
     hipLaunchKernelGGL(k_eval_advance, dim3((unsigned)((n_envs + FWG_EVAL_THREADS - 1) / FWG_EVAL_THREADS)), dim3(FWG_EVAL_THREADS), 0, (hipStream_t)stream,
                        (long)n_envs, (long)t, reward, done, term_code, metrics, active, length, termination, metrics_final, reward_trace, actions_io);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int64_t fwg_record_row_words(void) { return FWG_REC_WORDS; }
+
+static int record_args(const char* who, const fwg_handle* h, const void* ids, int n_tracked, const void* rows, const void* hdr, int64_t max_rows, RecCfg* rc) {
+    if (!h || !ids || !rows || !hdr) return fail_with(FWG_ERR_INVALID, std::string(who) + ": null argument");
+    if (n_tracked < 1 || n_tracked > FWG_REC_MAX_TRACKED)
+        return fail_with(FWG_ERR_INVALID, std::string(who) + ": n_tracked must be in 1 .. " + std::to_string(FWG_REC_MAX_TRACKED));
+    if (max_rows < 2) return fail_with(FWG_ERR_INVALID, std::string(who) + ": max_rows must be at least 2 (the reset row and one step)");
+    const fwg_layout& L = h->h.L;
+    *rc = RecCfg{L.sim, L.cold, L.derived, L.gym, h->h.store_derived, h->h.turbulence, h->h.auto_reset};
+    return FWG_OK;
+}
+
+int fwg_record_start(const fwg_handle* h, const int64_t* ids_dev, int n_tracked, const uint8_t* mask, float* rows, int32_t* hdr, int64_t max_rows,
+                     void* stream) {
+    RecCfg rc;
+    if (const int st = record_args("fwg_record_start", h, ids_dev, n_tracked, rows, hdr, max_rows, &rc)) return st;
+    hipLaunchKernelGGL(k_record_start, dim3((unsigned)n_tracked), dim3(64), 0, (hipStream_t)stream, rc, (const float*)h->arena, (long)h->n_envs,
+                       (const long long*)ids_dev, n_tracked, mask, rows, (int*)hdr, (long)max_rows);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_record(const fwg_handle* h, const int64_t* ids_dev, int n_tracked, const float* actions, const float* reward, const uint8_t* done,
+               const uint8_t* term_code, float* rows, int32_t* hdr, int64_t max_rows, void* stream) {
+    RecCfg rc;
+    if (const int st = record_args("fwg_record", h, ids_dev, n_tracked, rows, hdr, max_rows, &rc)) return st;
+    if (!actions || !reward || !done || !term_code) return fail_with(FWG_ERR_INVALID, "fwg_record: null argument");
+    hipLaunchKernelGGL(k_record, dim3((unsigned)n_tracked), dim3(64), 0, (hipStream_t)stream, rc, (const float*)h->arena, (long)h->n_envs,
+                       (const long long*)ids_dev, n_tracked, actions, reward, done, term_code, rows, (int*)hdr, (long)max_rows);
     HIP_TRY(hipGetLastError());
     return FWG_OK;
 }

@@ -3,7 +3,7 @@ module without a built library raises, there is no CPU fallback."""
 import ctypes as C
 import os
 
-FWG_ABI_VERSION = 24
+FWG_ABI_VERSION = 25
 N_VARS = 23
 N_RESET_VARS = 21
 N_PARAMS = 49
@@ -156,6 +156,10 @@ class PidGains(C.Structure):
                  "delta_e_min", "delta_e_max", "delta_a_min", "delta_a_max", "delta_t_min", "delta_t_max", "dt", "pad_"]]
 
 
+# the flight recorder's row and header (include/fwgym.h "Flight recorder")
+REC_WORDS, REC_HDR, REC_MAX_TRACKED = 32, 8, 64
+REC_SLAB, REC_OPEN, REC_OVERFLOW, REC_OVERFLOW_DONE, REC_INVALID = 1, 2, 4, 8, 16
+
 PPO_NSTAT = 4   # loss sums appended to a gradient buffer (include/fwgym.h "PPO update")
 
 
@@ -203,6 +207,9 @@ PROTOTYPES = {
     "fwg_gae": (_int, [_i64, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp]),
     "fwg_pid_act": (_int, [_i64, _vp, _int, C.POINTER(C.c_int32), _vp, _int, C.POINTER(C.c_int32), PidGains, _vp, _vp, _vp]),
     "fwg_eval_advance": (_int, [_i64, _i64] + [_vp] * 9 + [_i64, _vp, _vp]),
+    "fwg_record_row_words": (_i64, []),
+    "fwg_record_start": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _i64, _vp]),
+    "fwg_record": (_int, [_vp, _vp, _int] + [_vp] * 6 + [_i64, _vp]),
     "fwg_selftest_philox": (_int, [_vp, _vp, _i64, _vp]),
     "fwg_actor_create": (_int, [_int, _i64, _int, _int, _f32, _f32, _f32, _f32, C.POINTER(_vp)]),
     "fwg_actor_destroy": (None, [_vp]),

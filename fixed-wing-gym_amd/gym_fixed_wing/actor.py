@@ -225,6 +225,9 @@ class DeviceActor(object):
         """act() on the observation `vec` currently shows (and the reward / done flags of the step that led to it), then
         vec.step_device() under the sampled actions -- one launch (fwg_rollout_step; the body of the reference's training loop,
         examples/train_rl_controller.py:223-231).  Outputs as act(); afterwards vec._obs / _rew / _done hold the new step."""
+        if getattr(vec, "_recorder", None) is not None:
+            raise ValueError("rollout_step: a FlightRecorder is attached to this env and the one-launch step (fwg_rollout_step) "
+                             "cannot be recorded -- use the two-launch path (step_device + act)")
         m = self._mem
         nat.check(self._lib, self._lib.fwg_rollout_step(
             vec._handle, self._handle, self._p(norm_obs), self._p(action), self._p(value), self._p(logp), self._p(norm_reward),

@@ -6,16 +6,13 @@ One instance is a 1-env slice of the batched HIP path (FixedWingVecEnv with auto
 against the reference (`env = FixedWingAircraft(config_path); obs = env.reset(); obs, r, done, info = env.step(a)`)
 runs unchanged.  Throughput comes from FixedWingVecEnv; this class exists for API parity, evaluation and rendering.
 """
-import os
-
 import numpy as np
 
 from . import _native as nat
+from . import recorder as _rec
+from .recorder import _RECORDED   # noqa: F401  (the states whose histories are kept, shared with the device flight recorder)
 from .spaces import Box, DictSpace, Env, GoalEnv
 from .vec_env import FixedWingVecEnv
-
-_RECORDED = ["roll", "pitch", "yaw", "omega_p", "omega_q", "omega_r", "position_n", "position_e", "position_d",
-             "velocity_u", "velocity_v", "velocity_w", "Va", "alpha", "beta", "elevator", "aileron", "throttle"]
 
 
 class _StateView(object):
@@ -60,27 +57,8 @@ class _SimulatorView(object):
                     st.history.append(self._values[n])
 
     def constrained_command(self, action):
-        """What PyFly stores in simulator.state[actuator].history["command"] (read by the reference at
-        fixed_wing.py:828 and :1110): the inputs after action scaling (fixed_wing.py:349-354,439-459), the value limits of
-        elevator / aileron / throttle and of the two elevons, mapped back to elevator / aileron -- the same arithmetic the
-        step kernel applies (csrc/fwgym_physics.h constrain_commands)."""
-        ec = self._env._vec.env_config
-        a = np.asarray(action, dtype=np.float64).reshape(3)
-        if self._env.cfg["action"].get("scale_space", False):
-            lo, hi = self._env.cfg["action"].get("scale_low", -1), self._env.cfg["action"].get("scale_high", 1)
-            to_lo, to_hi = ec.action_scale_to_low, ec.action_scale_to_high
-            a = (to_hi - to_lo) * (np.clip(a, lo, hi) - lo) / (hi - lo) + to_lo
-
-        def lim(x, name):
-            v = ec.state[name]
-            if getattr(v, "value_min", None) is not None:
-                x = max(x, v.value_min)
-            if getattr(v, "value_max", None) is not None:
-                x = min(x, v.value_max)
-            return x
-        e, al, t = lim(a[0], "elevator"), lim(a[1], "aileron"), lim(a[2], "throttle")
-        er, el = lim(e - al, "elevon_right"), lim(e + al, "elevon_left")
-        return {"elevator": 0.5 * (er + el), "aileron": 0.5 * (el - er), "throttle": t}
+        """What PyFly stores in simulator.state[actuator].history["command"]: recorder.constrained_command."""
+        return _rec.constrained_command(self._env.cfg, self._env._vec.env_config, action)
 
     def record_command(self, action):
         cmd = self.constrained_command(action)
@@ -218,60 +196,10 @@ class FixedWingAircraft(Env):
             self.render_on_reset = True
             self.render_on_reset_kw = {"mode": mode, "show": show, "block": block, "close": close, "save_path": save_path}
             return None
-        if mode not in ("plot", "rgb_array"):
-            if mode == "animation":
-                raise NotImplementedError
-            raise ValueError("Unexpected value {} for mode".format(mode))
-        import matplotlib
-        if not show:
-            matplotlib.use("Agg", force=False)
-        import matplotlib.pyplot as plt
-        import matplotlib.gridspec
-        rcfg = self.cfg["render"]
-        groups = [("roll", "pitch"), ("Va",), ("omega_p", "omega_q", "omega_r"), ("elevator", "aileron", "throttle")]
-        extra = int(bool(rcfg["plot_action"])) + int(bool(rcfg["plot_reward"]))
-        fig = plt.figure(figsize=(9, 16))
-        gs = matplotlib.gridspec.GridSpec(len(groups) + extra, 1)
-        for gi, names in enumerate(groups):
-            ax = plt.subplot(gs[gi, 0])
-            for n in names:
-                h = self.simulator.state[n].history
-                y = h["value"] if isinstance(h, dict) else h
-                line, = ax.plot(range(len(y)), y, label=n)
-                if rcfg["plot_target"] and n in self.history["target"]:
-                    tgt = np.array(self.history["target"][n])
-                    ax.plot(range(len(tgt)), tgt, "--", color=line.get_color(), label=n + " target")
-                    if rcfg["plot_goal"] and self.goal_enabled and n in self.history["goal"]:
-                        p = self._vec.env_config.target_props_init["states"][n]
-                        b = np.radians(p["bound"]) if p.get("convert_to_radians", False) else p["bound"]
-                        ok = np.array(self.history["goal"][n], dtype=bool)[:len(tgt)]
-                        ax.fill_between(range(len(tgt)), tgt - b, tgt + b, where=ok, alpha=0.2, color=line.get_color())
-            ax.legend(loc="upper right")
-        if rcfg["plot_action"]:
-            ax = plt.subplot(gs[-extra, 0], title="Actions")
-            y = np.array(self.history["action"]).reshape(-1, 3)
-            for i, a in enumerate(self.cfg["action"]["states"]):
-                ax.plot(range(len(y)), y[:, i], label=a["name"])
-            ax.legend()
-        if rcfg["plot_reward"]:
-            ax = plt.subplot(gs[-1, 0], title="Reward")
-            ax.plot(range(len(self.history["reward"])), self.history["reward"])
-        self.viewer = {"fig": fig, "gs": gs}
-        if save_path is not None:
-            d = os.path.dirname(save_path)
-            if d and not os.path.isdir(d):
-                os.makedirs(d)
-            ext = os.path.splitext(save_path)[1]
-            plt.savefig(save_path, bbox_inches="tight", **({"format": ext[1:]} if ext else {}))
-        if mode == "rgb_array":
-            return None
-        if show:
-            plt.show(block=block)
-        if close:
-            plt.close(fig)
-            self.viewer = None
-            return None
-        return fig
+        states = {n: st.history for n, st in self.simulator.state.items() if st.history is not None}
+        out, self.viewer = _rec.plot_episode(self.cfg, self._vec.env_config, states, self.history, mode=mode, show=show, close=close,
+                                             block=block, save_path=save_path)
+        return out
 
     def save_history(self, path, states, save_targets=True):
         """reference fixed_wing.py:654-672: .npy dict of state histories (+ '<state>_target' entries)."""
@@ -279,15 +207,8 @@ class FixedWingAircraft(Env):
             self.save_on_reset = True
             self.save_on_reset_kw = {"path": path, "states": states, "save_targets": save_targets}
             return
-        res = {}
-        for s in ([states] if isinstance(states, str) else states):
-            h = self.simulator.state[s].history
-            res[s] = list(h["value"] if isinstance(h, dict) else h)
-        if save_targets:
-            for s in self.target:
-                if s in res:
-                    res[s + "_target"] = self.history["target"][s]
-        np.save(path, res)
+        hist = {n: st.history for n, st in self.simulator.state.items()}
+        _rec.save_history_file(self.cfg, self._vec.env_config, hist, self.history, path, states, save_targets)
 
     def get_initial_state(self):
         """reference fixed_wing.py:848-862 (test-set record format)."""

@@ -247,8 +247,14 @@ class FusedRollout(object):
         else:
             actor.set_obs_log(vec)
         can_fuse = self._attached and hasattr(actor, "rollout_available") and actor.rollout_available(vec)
+        # a FlightRecorder (gym_fixed_wing.recorder) records behind every fwg_step launch: the one-launch step has no such
+        # boundary, so "auto" / None take the two-launch path with a recorder attached and fused=True is refused
+        recording = getattr(vec, "_recorder", None) is not None
         if fused == "auto":   # the one-launch step wherever it is available
-            fused = bool(can_fuse)
+            fused = bool(can_fuse) and not recording
+        if fused and recording:
+            raise ValueError("FusedRollout(fused=True): a FlightRecorder is attached to this env and the one-launch step "
+                             "(fwg_rollout_step) cannot be recorded -- use the two-launch path (fused=False, None or 'auto')")
         if fused and not can_fuse:
             raise ValueError("FusedRollout(fused=True): fwg_rollout_step is not available for this env / head (needs a specialised "
                              "kernel, the dense observation batch and an attached head)")
@@ -257,7 +263,7 @@ class FusedRollout(object):
         # in isolation and in suite context: profiles/r05_soak.txt) -- until it is, the path whose every launch boundary is a
         # kernel boundary stays the default and the one-launch step is something a caller asks for (bench.py does, and says so)
         import os
-        self.fused = (can_fuse and os.environ.get("FWGYM_ROLLOUT_FUSED", "0") == "1") if fused is None else bool(fused)
+        self.fused = (can_fuse and not recording and os.environ.get("FWGYM_ROLLOUT_FUSED", "0") == "1") if fused is None else bool(fused)
         self.tap = tap
         if graph:
             self._capture()

@@ -212,6 +212,7 @@ class FixedWingVecEnv(object):
                                                   int(env_id_base), ctypes.byref(self._handle)))
         self.check_actions = False
         self._pending = None
+        self._recorder = None   # a gym_fixed_wing.recorder.FlightRecorder attaches itself here: one more launch per reset / step
         self.seed(seed)
 
     def _row_log_applies(self):
@@ -381,6 +382,8 @@ class FixedWingVecEnv(object):
         nat.check(self._lib, self._lib.fwg_reset(self._handle, m.ptr(mask_t) if mask_t is not None else null,
                                                  m.ptr(st) if st is not None else null,
                                                  m.ptr(tg) if tg is not None else null, m.ptr(self._obs_buf), m.stream()))
+        if self._recorder is not None:
+            self._recorder._on_reset(mask_t)
         self._refresh_obs_view()
         if st is not None or tg is not None or mask_t is not None:
             m.sync()  # the temporaries above must outlive the launch
@@ -425,6 +428,8 @@ class FixedWingVecEnv(object):
         nat.check(self._lib, self._lib.fwg_step(self._handle, m.ptr(act), m.ptr(self._obs_buf), m.ptr(self._rew), m.ptr(self._done),
                                                 m.ptr(self._term), m.ptr(self._term_obs), m.ptr(self._metrics),
                                                 m.ptr(self._target), m.stream()))
+        if self._recorder is not None:
+            self._recorder._on_step(act)
         self._refresh_obs_view()
         self._pending = act  # keeps the action buffer alive until the kernel has consumed it
 
@@ -449,6 +454,8 @@ class FixedWingVecEnv(object):
                                                 m.ptr(self._term), m.ptr(self._term_obs), m.ptr(self._metrics),
                                                 m.ptr(self._target) if target_out else ctypes.c_void_p(),   # (default: targets stay in the state arena)
                                                 m.stream()))
+        if self._recorder is not None:
+            self._recorder._on_step(actions)
         if want_obs:
             self._refresh_obs_view()
         return self._obs, self._rew, self._done
@@ -641,8 +648,15 @@ class FixedWingVecEnv(object):
             obs = self.reset(indices=indices, states=state, targets=target)
             idx = range(self.num_envs) if indices is None else np.atleast_1d(indices)
             return [obs[i] for i in idx]
-        if method_name == "render":
-            return [None]
+        if method_name in ("render", "save_history"):
+            # the episode history lives in a FlightRecorder (gym_fixed_wing.recorder); without one tracking the env, or before
+            # its first episode has ended, there is nothing to show
+            rec = self._recorder
+            i = 0 if indices is None else int(np.atleast_1d(indices)[0])
+            k = rec.slot_of(i) if rec is not None else None
+            if k is None or rec.completed(k) == 0:
+                return [None]
+            return [getattr(rec, method_name)(*args, k=k, **kwargs)]
         raise NotImplementedError(method_name)
 
     def env_is_wrapped(self, wrapper_class, indices=None):

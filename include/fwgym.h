@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FWG_ABI_VERSION 24
+#define FWG_ABI_VERSION 25
 
 #define FWG_N_VARS 23        /* simulator variables, see fwg_var */
 #define FWG_N_RESET_VARS 21  /* the keys of reset(state=...) records (fixed_wing.py:287,308; test-set format) */
@@ -622,6 +622,57 @@ int fwg_pid_act(int64_t n_envs, const float* obs, int obs_stride, const int32_t*
 int fwg_eval_advance(int64_t n_envs, int64_t t, const float* reward, const uint8_t* done, const uint8_t* term_code, const float* metrics,
                      uint8_t* active, int32_t* length, uint8_t* termination, float* metrics_final, float* reward_trace, int64_t trace_steps,
                      float* actions_io, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Flight recorder: the episode history of up to 64 envs of a handle, kept on the device by one small launch behind every
+ * fwg_reset / fwg_step -- what the reference's FixedWingAircraft keeps on the host for render / save_history
+ * (fixed_wing.py:572-672) and its training callback plots every few minutes (examples/train_rl_controller.py:31-110).  Both
+ * calls are stateless launches on `stream` over caller-owned device buffers: no allocation, no synchronisation, no host read,
+ * and nothing passed by value changes between steps, so they may sit inside a captured sequence of fwg_step calls (one more
+ * node in sequence) and replay correctly.  Buffers, for n_tracked = K envs and max_rows rows (zero `hdr` before the
+ * first call: an all-zero header is "never started"):
+ *   ids  : int64 [K]                        env indices of this handle; an index outside [0, N) records nothing and sets
+ *                                           FWG_REC_INVALID in its slot.  An index may be listed twice (two independent slots)
+ *   rows : float32 [2][K][max_rows][32]     two slabs per tracked env: the episode in progress and the last completed one
+ *   hdr  : int32 [K][8]                     0: flags  FWG_REC_SLAB (bit 0: index of the OPEN slab) | FWG_REC_OPEN (an episode is
+ *                                              open) | FWG_REC_OVERFLOW (the open episode lost rows) | FWG_REC_OVERFLOW_DONE (the
+ *                                              completed episode did) | FWG_REC_INVALID
+ *                                           1: rows in the open slab          2: rows in the completed slab
+ *                                           3: FWG_TERM_* of the completed episode
+ *                                           4: episode serial of the open slab (the arena's episode word, layout.cold + 3)
+ *                                           5: episode serial of the completed slab
+ *                                           6: episodes completed since hdr was zeroed      7: 0
+ * Row (32 words, 128 B):
+ *   0..15   arena sim words 0..15: e0 e1 e2 e3 p q r pn pe pd u v w elevon_r elevon_l throttle
+ *   16..21  roll pitch yaw Va alpha beta: copied from layout.derived with store_derived; without it roll / pitch / yaw are
+ *           computed from the committed quaternion, and Va / alpha / beta are computed from the committed state and the steady wind
+ *           (turbulence off) or copied from the second derived group, which the step keeps whenever turbulence is on
+ *   22..24  targets 0..2 (layout.gym + 0..2)
+ *   25..27  the raw action of the step       28  its reward
+ *   29      the steps_count | steps_for_target << 16 word of the arena, as bits
+ *   30      done | term_code << 8, as bits   31  0
+ * Row 0 of an episode is the state and target at reset (words 25..28 NaN, word 30 zero); row t >= 1 the sample after step t.
+ * THE TERMINAL ROW (the one difference from the single-env class): words 25..31 are always written, but the state and target
+ * words 0..24 are written only when the handle's auto_reset is off and the episode ended with FWG_TERM_STEPS or
+ * FWG_TERM_SUCCESS; otherwise they are NaN.  With auto_reset on, the arena holds the NEXT episode by the time fwg_step
+ * returns, so the terminal state exists nowhere (and word 29 is the next episode's); after a simulator failure the state was
+ * never committed, and the single-env class records none either (fixed_wing.py:409-416).
+ * A row past max_rows is dropped and FWG_REC_OVERFLOW set; nothing is ever written past a slab.
+ * ------------------------------------------------------------------------------------------------------------------ */
+enum { FWG_REC_SLAB = 1, FWG_REC_OPEN = 2, FWG_REC_OVERFLOW = 4, FWG_REC_OVERFLOW_DONE = 8, FWG_REC_INVALID = 16 };
+int64_t fwg_record_row_words(void);            /* 32 */
+/* After fwg_reset, with the same mask (NULL = all): every selected tracked env drops the episode in progress WITHOUT completing
+ * it, opens its open slab again and writes row 0 from the arena.  Unselected envs' slabs and headers are left untouched. */
+int fwg_record_start(const fwg_handle* h, const int64_t* ids_dev, int n_tracked, const uint8_t* mask,
+                     float* rows, int32_t* hdr, int64_t max_rows, void* stream);
+/* After every fwg_step, with the action batch that step consumed and its reward_out / done_out / term_code_out.  Per tracked env
+ * with an open episode: appends a row; where done, closes the episode (length, termination and serial into the header, completed
+ * count + 1), flips the slabs (no copy) and, with auto_reset on, opens the other slab with row 0 from the arena (the new
+ * episode's reset state and target).  With auto_reset off the episode stays closed until the next fwg_record_start: a finished
+ * env keeps reporting done and only the first end counts.
+ * Both: FWG_ERR_INVALID for NULL buffers, n_tracked outside 1 .. 64, max_rows < 2. */
+int fwg_record(const fwg_handle* h, const int64_t* ids_dev, int n_tracked, const float* actions, const float* reward,
+               const uint8_t* done, const uint8_t* term_code, float* rows, int32_t* hdr, int64_t max_rows, void* stream);
 
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);

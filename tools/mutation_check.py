@@ -7,7 +7,7 @@ tests/test_ppo_hip_contract.py (the ppo_cnn_* ones, slips in the backward pass t
 tests/test_ppo_hip_cnn.py).  The head mutants (head_*: the rollout head, fwgym_actor.h) likewise, against the emulated forms of
 tests/test_actor_contract.py (the head_cnn_* ones, slips in the CNN head's own code, those of tests/test_actor_contract_cnn.py); they are
 built for the host emulation only.  The eval_* mutants (the evaluation protocol on the device,
-fwgym_eval.h) run tests/test_eval_device.py.
+fwgym_eval.h) run tests/test_eval_device.py; the recorder_* mutants (the device flight recorder, fwgym_record.h) tests/test_recorder.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
@@ -146,6 +146,20 @@ MUTANTS = {
          "    const float i_phi = integ[e] + g.dt * e_phi, i_theta = integ[N + e] + g.dt * e_theta, i_va = integ[2 * N + e] + g.dt * e_va;"),
         ("fwgym_eval.h", "    integ[e] = i_phi + g.dt * e_phi;\n    integ[N + e] = i_theta + g.dt * e_theta;\n    integ[2 * N + e] = i_va + g.dt * e_va;\n",
          "    integ[e] = i_phi;\n    integ[N + e] = i_theta;\n    integ[2 * N + e] = i_va;\n")],
+    # ---- the device flight recorder (fwgym_record.h); they run the emulated forms, tests/test_recorder.py.
+    # an episode end leaves the slabs where they are: the next episode overwrites the completed one
+    "recorder_no_slab_flip": [
+        ("fwgym_record.h", "    f = (f & ~(FWG_REC_F_OVERFLOW | FWG_REC_F_OPEN)) ^ FWG_REC_F_SLAB;", "    f = (f & ~(FWG_REC_F_OVERFLOW | FWG_REC_F_OPEN));")],
+    # after an auto-reset the new episode's row 0 is not written (the other slab keeps an older episode's row 0)
+    "recorder_row0_not_rewritten": [
+        ("fwgym_record.h", "    } else if (reopen) {\n", "    } else if (reopen && false) {\n")],
+    # the terminal row takes its state words from the arena under auto-reset too (the NEXT episode's reset state)
+    "recorder_terminal_state_under_auto_reset": [
+        ("fwgym_record.h", "    const bool state = !d || (!rc.auto_reset && (tc == FWG_TERM_STEPS || tc == FWG_TERM_SUCCESS));",
+         "    const bool state = !d || (tc == FWG_TERM_STEPS || tc == FWG_TERM_SUCCESS);")],
+    # store_derived off in turbulence: Va read where store_derived would keep it (a word the step does not write then)
+    "recorder_turbulent_va_from_the_first_group": [
+        ("fwgym_record.h", "return rec_arena(S, N, e, rc.derived + (i == 3 ? 6 : i));", "return rec_arena(S, N, e, rc.derived + i);")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -156,8 +170,9 @@ _CURRICULUM_TESTS = ["-k", "sparse or another_seed", os.path.join(ROOT, "tests",
 _HEAD_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract.py")]
 _CNN_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_cnn.py")]
 _EVAL_TESTS = [os.path.join(ROOT, "tests", "test_eval_device.py")]
+_RECORDER_TESTS = [os.path.join(ROOT, "tests", "test_recorder.py")]
 _HEAD_CNN_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract_cnn.py")]
-TESTS = {name: (_EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+TESTS = {name: (_RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
