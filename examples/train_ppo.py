@@ -33,7 +33,8 @@ from gym_fixed_wing.rollout import CnnMlpPolicy  # noqa: E402
 
 def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, learning_rate=5e-4, n_steps=128, curriculum=True,
           config=None, log=print, rank=0, world=1, local=0, fused=None, ent_coef=0.01, on_update=None, update="torch", policy="mlp",
-          test_set=None, test_turbulence="none", render_dir=None, render_every=600.0):
+          test_set=None, test_turbulence="none", render_dir=None, render_every=600.0, monitor=False, log_dir=None, log_interval=50,
+          checkpoint_every=None, checkpoint_path=None):
     """policy: "mlp" (MlpPolicy on the examples config's 12-vector) or "cnn" (CnnMlpPolicy on the cnn config's 5 x 12 matrix
     observations: the reference's --policy CNN, train_rl_controller.py:179-197).  update: "torch" or "hip" (for the cnn policy
     "hip" is PPO's "hip_cnn").  config: preset name, default by policy.
@@ -43,7 +44,13 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
     protocol on the device); the table goes into that update's info["test"].
     render_dir: rank 0 records env 0 on the device (gym_fixed_wing.recorder.FlightRecorder) and, whenever `render_every` seconds
     have passed and env 0 has finished another episode, saves that episode's figure as <render_dir>/<num_timesteps>.png -- the
-    reference's render_interval = 600 s of training episodes (train_rl_controller.py:95-104)."""
+    reference's render_interval = 600 s of training episodes (train_rl_controller.py:95-104).
+    monitor: PPO(monitor=True) -- every info carries the finished episodes' mean return and length (stable-baselines' ep_rewmean /
+    eplenmean, gym_fixed_wing.monitor) and all five info_kw measures per target state (info["ep_info"]).
+    log_dir: rank 0 appends every update's info to <log_dir>/progress.csv and prints the reference's block of the five measures
+    every `log_interval` updates (monitor.ProgressLog; the first job of the reference's monitor_training).
+    checkpoint_every: rank 0 saves the model to `checkpoint_path` whenever that many seconds have passed (the reference's
+    save_interval = 300 s)."""
     if isinstance(test_set, str):
         with open(test_set) as f:
             test_set = json.load(f)
@@ -67,8 +74,13 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
     if policy == "cnn" and update == "hip":
         update = "hip_cnn"
     ppo = PPO(vec, policy=net, seed=seed, curriculum=sched, n_steps=n_steps, nminibatches=nminibatches, noptepochs=noptepochs,
-              learning_rate=learning_rate, fused=fused, ent_coef=ent_coef, update=update)
+              learning_rate=learning_rate, fused=fused, ent_coef=ent_coef, update=update, monitor=monitor)
     t0 = time.perf_counter()
+    progress = None
+    if log_dir is not None and rank == 0:
+        from gym_fixed_wing.monitor import ProgressLog
+        progress = ProgressLog(log_dir, log_interval, out=log)
+    saved = {"at": t0, "files": 0}
     window = []    # success over the last finished episodes (the reference's ep_info_buf holds the last 100)
     tests_done = [0]
     rendered = {"at": t0, "episodes": 0, "files": []}
@@ -95,10 +107,18 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
         if info["episodes"] > 0:
             window.append((info["episodes"], info["success"]["all"], info["level"]))
         if rank == 0 and log is not None and (info["episodes"] > 0 or info["update"] % 20 == 0):
-            log("update {:4d}  steps {:10.3e}  level {:.2f}  episodes {:6d}  success_all {}  pg {:+.4f}  vf {:.4f}  kl {:.4f}  std-entropy {:+.2f}  {:.0f} s".format(
+            ep = ""
+            if info.get("ep_rew_mean") is not None:
+                ep = "  ep_rew {:+.3f}  ep_len {:.1f}".format(info["ep_rew_mean"], info["ep_len_mean"])
+            log("update {:4d}  steps {:10.3e}  level {:.2f}  episodes {:6d}  success_all {}  pg {:+.4f}  vf {:.4f}  kl {:.4f}  std-entropy {:+.2f}  {:.0f} s{}".format(
                 info["update"], info["timesteps"], info["level"], info["episodes"],
                 "{:.3f}".format(info["success"]["all"]) if info["episodes"] else "  -  ", info["pg_loss"], info["vf_loss"], info["approx_kl"],
-                info["entropy"], time.perf_counter() - t0))
+                info["entropy"], time.perf_counter() - t0, ep))
+        if progress is not None:
+            progress(info)
+        if checkpoint_every is not None and checkpoint_path and rank == 0 and time.perf_counter() - saved["at"] >= checkpoint_every:
+            ppo.save(checkpoint_path)
+            saved.update(at=time.perf_counter(), files=saved["files"] + 1)
         if on_update is not None:
             on_update(ppo, info)
 
@@ -106,7 +126,8 @@ def train(envs=4096, timesteps=100e6, seed=0, nminibatches=128, noptepochs=4, le
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     return ppo, {"seconds": dt, "env_steps_per_s": ppo.num_timesteps / dt, "updates": ppo.updates, "episodes_log": window,
-                 "rendered": rendered["files"]}
+                 "rendered": rendered["files"], "checkpoints": saved["files"],
+                 "progress": None if progress is None else progress.path}
 
 
 def main():
@@ -126,6 +147,10 @@ def main():
     ap.add_argument("--test-turbulence", default="none", choices=["none", "light", "moderate", "severe"])
     ap.add_argument("--render-dir", default=None, help="save the figure of a training episode of env 0 as DIR/<num_timesteps>.png (rank 0)")
     ap.add_argument("--render-every", type=float, default=600.0, help="seconds between two rendered episodes (the reference's interval)")
+    ap.add_argument("--log-dir", default=None, help="append every update to DIR/progress.csv and print the per-state measures (rank 0)")
+    ap.add_argument("--log-interval", type=int, default=50, help="updates between two printed blocks of the per-state measures")
+    ap.add_argument("--checkpoint-every", type=float, default=None, metavar="SECONDS",
+                    help="save to --out whenever that many seconds have passed (the reference saves every 300 s; rank 0)")
     ap.add_argument("--out", default=None, help="save weights + VecNormalize statistics (.npz)")
     ap.add_argument("--curve", default=None, help="write the learning curve (JSON)")
     args = ap.parse_args()
@@ -137,7 +162,8 @@ def main():
     ppo, res = train(args.envs, args.timesteps, args.seed, args.nminibatches, args.noptepochs, args.lr, curriculum=not args.disable_curriculum,
                      rank=rank, world=world, local=local, ent_coef=args.ent_coef, update=args.update, policy=args.policy,
                      test_set=args.test_set, test_turbulence=args.test_turbulence, render_dir=args.render_dir,
-                     render_every=args.render_every)
+                     render_every=args.render_every, monitor=True, log_dir=args.log_dir, log_interval=args.log_interval,
+                     checkpoint_every=args.checkpoint_every, checkpoint_path=args.out)
     if rank == 0:
         print("{:.3e} env-steps in {:.1f} s = {:.3e} env-steps/s INCLUDING the optimiser ({} updates)".format(
             ppo.num_timesteps, res["seconds"], res["env_steps_per_s"], res["updates"]))

@@ -21,6 +21,7 @@
 #include "fwgym_learner.h" // the PPO update on the device (fwg_ppo_*)
 #include "fwgym_eval.h"    // the evaluation protocol on the device (fwg_pid_act, fwg_eval_advance)
 #include "fwgym_record.h"  // the device flight recorder (fwg_record_start, fwg_record)
+#include "fwgym_monitor.h" // the device training monitor (fwg_monitor_fold, fwg_monitor_take)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
@@ -2274,6 +2275,29 @@ int fwg_gae(int64_t n_steps, int64_t n_envs, const float* rewards, const float* 
     if (n_steps < 1 || n_envs < 1) return fail_with(FWG_ERR_INVALID, "fwg_gae: n_steps and n_envs must be positive");
     hipLaunchKernelGGL(k_gae, dim3((unsigned)((n_envs + 63) / 64)), dim3(256), 4 * 64 * 2 * sizeof(float), (hipStream_t)stream, rewards, values, dones, last_value,
                        gamma, lam, adv_out, ret_out, (long)n_steps, (long)n_envs);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int64_t fwg_monitor_scratch_bytes(int64_t n_envs) {
+    return n_envs < 1 ? 0 : ((n_envs + 63) / 64) * FWG_N_MONITOR * (int64_t)sizeof(long long);
+}
+
+int fwg_monitor_fold(int64_t n_steps, int64_t n_envs, const float* raw_rewards, const uint8_t* dones, int64_t* ep_q_io, int32_t* ep_len_io,
+                     void* scratch, void* stream) {
+    if (!raw_rewards || !dones || !ep_q_io || !ep_len_io || !scratch) return fail_with(FWG_ERR_INVALID, "fwg_monitor_fold: null argument");
+    if (n_steps < 1 || n_envs < 1) return fail_with(FWG_ERR_INVALID, "fwg_monitor_fold: n_steps and n_envs must be positive");
+    hipLaunchKernelGGL(k_monitor_fold, dim3((unsigned)((n_envs + 63) / 64)), dim3(256), 4 * 4 * 64 * sizeof(long long), (hipStream_t)stream,
+                       raw_rewards, dones, (long long*)ep_q_io, (int*)ep_len_io, (long long*)scratch, (long)n_steps, (long)n_envs);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_monitor_take(int64_t n_envs, void* scratch, double* out, void* stream) {
+    if (!scratch || !out) return fail_with(FWG_ERR_INVALID, "fwg_monitor_take: null argument");
+    if (n_envs < 1) return fail_with(FWG_ERR_INVALID, "fwg_monitor_take: n_envs must be positive");
+    hipLaunchKernelGGL(k_monitor_take, dim3(1), dim3(256), 4 * FWG_N_MONITOR * sizeof(long long), (hipStream_t)stream, (long long*)scratch, out,
+                       (long)((n_envs + 63) / 64));
     HIP_TRY(hipGetLastError());
     return FWG_OK;
 }

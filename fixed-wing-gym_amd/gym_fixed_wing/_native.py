@@ -3,7 +3,7 @@ module without a built library raises, there is no CPU fallback."""
 import ctypes as C
 import os
 
-FWG_ABI_VERSION = 25
+FWG_ABI_VERSION = 26
 N_VARS = 23
 N_RESET_VARS = 21
 N_PARAMS = 49
@@ -17,6 +17,7 @@ END_WINDOW = 50
 N_DRYDEN = 8
 N_METRICS = 28
 N_REDUCE = 16
+N_MONITOR = 8
 
 VARS = ["roll", "pitch", "yaw", "omega_p", "omega_q", "omega_r", "position_n", "position_e", "position_d",
         "velocity_u", "velocity_v", "velocity_w", "Va", "alpha", "beta", "elevator", "aileron", "throttle",
@@ -210,6 +211,9 @@ PROTOTYPES = {
     "fwg_record_row_words": (_i64, []),
     "fwg_record_start": (_int, [_vp, _vp, _int, _vp, _vp, _vp, _i64, _vp]),
     "fwg_record": (_int, [_vp, _vp, _int] + [_vp] * 6 + [_i64, _vp]),
+    "fwg_monitor_scratch_bytes": (_i64, [_i64]),
+    "fwg_monitor_fold": (_int, [_i64, _i64] + [_vp] * 6),
+    "fwg_monitor_take": (_int, [_i64, _vp, _vp, _vp]),
     "fwg_selftest_philox": (_int, [_vp, _vp, _i64, _vp]),
     "fwg_actor_create": (_int, [_int, _i64, _int, _int, _f32, _f32, _f32, _f32, C.POINTER(_vp)]),
     "fwg_actor_destroy": (None, [_vp]),

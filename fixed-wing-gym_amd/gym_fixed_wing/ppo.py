@@ -12,7 +12,10 @@ script does with `PPO2(MlpPolicy, VecNormalize(SubprocVecEnv(...))).learn(total_
               HipLearner (PPO(update="hip"); "hip_cnn" for a CnnMlpPolicy) runs them as HIP kernels (forward / backward on the
               matrix cores, the conv on the VALU, clip and Adam on the device, one captured graph per update, the head repacked
               on the device);
-  curriculum  distributed.gather_success (one RCCL all-gather of 64 B per rank) + CurriculumSchedule after every rollout.
+  curriculum  distributed.gather_success (one RCCL all-gather of 64 B per rank) + CurriculumSchedule after every rollout;
+  monitor     PPO(monitor=True): monitor.EpisodeMonitor -- the rollout keeps the raw rewards (written by the step kernel itself),
+              fwg_monitor_fold folds them once per rollout, and learn() reports the episodes' mean return and length (PPO2's
+              ep_rewmean / eplenmean) and all five info_kw measures per target state.
 
 PPO is the training loop and the policy of an update (hyper-parameters, permutations, minibatch split); a step's mechanics are
 the updater's (PPO.learner).  The torch policy is the master copy of the weights; the updater leaves them in the HIP head after
@@ -64,14 +67,20 @@ def gae(lib, mem, rewards, values, dones, last_value, gamma, lam, adv_out=None, 
     return adv_out, ret_out
 
 
+def _blank(summary):
+    """A gather_success summary with every mean None (no episode ended: the means would be 0 / 0)."""
+    return {k: ({s: None for s in v} if isinstance(v, dict) else v) for k, v in summary.items()}
+
+
 class PPO(object):
     """PPO2-style learner for a FixedWingVecEnv: MlpPolicy on the (flattened) observation by default, or
     policy=CnnMlpPolicy(...) on 5 x 12 matrix observations (train_rl_controller.py --policy CNN; update="torch" or "hip_cnn").  `learn(total_timesteps)` alternates
     rollouts of n_steps x num_envs transitions with noptepochs x nminibatches gradient steps; `callback(self, info)` runs after
-    every update (the reference's monitor_training)."""
+    every update (the reference's monitor_training).  monitor=True: the rollout keeps its raw rewards, collect() folds them
+    (monitor.EpisodeMonitor) and learn() adds the episodes' return / length statistics and info["ep_info"] to every info."""
 
     def __init__(self, vec, policy=None, seed=0, fused=None, graph=True, curriculum=None, group=None, precise=True,
-                 graph_update=True, update="torch", **kw):
+                 graph_update=True, update="torch", monitor=False, **kw):
         from .actor import DeviceActor
         hp = dict(PPO2_DEFAULTS)
         unknown = set(kw) - set(hp)
@@ -94,8 +103,12 @@ class PPO(object):
         self.actor = DeviceActor.for_env(vec, seed=seed, gamma=hp["gamma"], precise=precise)
         self.actor.load_policy(self.policy)
         self._rollout_kw = dict(graph=bool(graph) and self._torch_dev.type == "cuda", fused=fused)
-        self.rollout = FusedRollout(vec, self.actor, self.n_steps, **self._rollout_kw)
-        self._spec_at_capture = vec.spec_index
+        self.monitor = None
+        if monitor:
+            from .monitor import EpisodeMonitor
+            self.monitor = EpisodeMonitor(vec)
+            self._rollout_kw["raw_rewards"] = True   # (in the dictionary: the rollout built anew after a curriculum change keeps them)
+        self._build_rollout()
         if update in ("hip", "hip_cnn"):   # (the module's parameters become views of its flat buffer here, before the broadcast below writes through them)
             self.learner = HipLearner(vec._lib, self.actor, self.policy, self._torch_dev, graph=graph_update, lr=hp["learning_rate"])
         else:
@@ -114,9 +127,17 @@ class PPO(object):
                 torch.distributed.broadcast(p.data, src=0, group=group)
             self.actor.load_policy(self.policy)
 
+    def _build_rollout(self):
+        self.rollout = FusedRollout(self.vec, self.actor, self.n_steps, **self._rollout_kw)
+        self._spec_at_capture = self.vec.spec_index
+        if self.monitor is not None and self.rollout.warmup is not None:   # the env steps a capture takes outside the buffers
+            self.monitor.fold(*self.rollout.warmup)
+
     def collect(self):
         """One rollout + advantages.  Returns the flattened training batch (views of the rollout buffers, no copies)."""
         buf = self.rollout.run()
+        if self.monitor is not None:   # stream-ordered behind the rollout, before the update
+            self.monitor.fold(buf["raw_rewards"], buf["dones"])
         gae(self.vec._lib, self.vec._mem, buf["rewards"], buf["values"], buf["dones"], self.rollout.last_value,
             self.hp["gamma"], self.hp["lam"], self.adv, self.ret)
         T, N = self.n_steps, self.vec.num_envs
@@ -146,14 +167,21 @@ class PPO(object):
             if summary["episodes"] > 0:
                 info["success"] = dict(summary["success"])
                 info["control_variation"] = summary["control_variation"]["all"]
+            if self.monitor is not None:
+                took = self.monitor.take(self.group)
+                # (info["episodes"] stays gather_success's count, which "success" goes with; the monitor's own -- the episodes that
+                # ended inside the folded buffers with a finite return -- is "monitor_episodes")
+                info.update({("monitor_episodes" if k == "episodes" else k): v for k, v in took.items()})
+                recent = self.monitor.window(100)
+                info["ep_rew_mean_100"], info["ep_len_mean_100"] = recent["ep_rew_mean"], recent["ep_len_mean"]
+                info["ep_info"] = summary if summary["episodes"] > 0 else _blank(summary)
             if self.curriculum is not None:
                 info["level"] = self.curriculum.update(self.vec, summary)
                 if self._rollout_kw["graph"] and self.vec.spec_index != self._spec_at_capture:
                     # (a captured rollout holds a kernel INSTANCE; the curriculum's ranges are read from memory and do not move it --
                     # a preset stays on its frozen kernel at every level, tests/test_shape_instance.py -- but a schedule whose
                     # update changes a folded value would: capture anew, fwg_replay_check refuses otherwise)
-                    self.rollout = FusedRollout(self.vec, self.actor, self.n_steps, **self._rollout_kw)
-                    self._spec_at_capture = self.vec.spec_index
+                    self._build_rollout()
             self.history.append(info)
             if log is not None:
                 log(info)

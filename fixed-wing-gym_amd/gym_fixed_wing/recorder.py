@@ -269,9 +269,10 @@ class FlightRecorder(object):
         nat.check(self._lib, self._lib.fwg_record_start(v._handle, m.ptr(self.ids), self.K, m.ptr(mask_t) if mask_t is not None else None,
                                                         m.ptr(self.rows), m.ptr(self.hdr), self.max_rows, m.stream()))
 
-    def _on_step(self, actions):
+    def _on_step(self, actions, reward=None):
+        """`reward`: where that step wrote its rewards (step_device's reward_out; default the env's own buffer)."""
         v, m = self.vec, self.vec._mem
-        nat.check(self._lib, self._lib.fwg_record(v._handle, m.ptr(self.ids), self.K, m.ptr(actions), m.ptr(v._rew), m.ptr(v._done),
+        nat.check(self._lib, self._lib.fwg_record(v._handle, m.ptr(self.ids), self.K, m.ptr(actions), m.ptr(v._rew if reward is None else reward), m.ptr(v._done),
                                                   m.ptr(v._term), m.ptr(self.rows), m.ptr(self.hdr), self.max_rows, m.stream()))
 
     # -- reading ------------------------------------------------------------------------------------------------------------

@@ -226,13 +226,23 @@ class FusedRollout(object):
 
     `fused` (opt-in: fused=True, fused="auto" = wherever fwg_rollout_available, or FWGYM_ROLLOUT_FUSED=1): act t and env step t run as ONE launch (fwg_rollout_step) -- a rollout is
     then [env step 0] [act + step] x (n - 1) [act n]: n + 1 launches instead of 2 n, bit-identical buffers.  `tap(t, obs, rew,
-    done)` (eager mode only) is called after every env step with the env's raw output tensors (tests, logging)."""
+    done)` (eager mode only) is called after every env step with the env's raw output tensors (tests, logging).
 
-    def __init__(self, vec, actor, n_steps, graph=False, fused=None, tap=None):
+    `raw_rewards=True`: the rollout also owns buf["raw_rewards"] (float32 [n_steps, N]) and env step t writes its reward into
+    row t INSTEAD of vec._rew (fwg_step's reward_out argument: the same bytes to another address, no extra launch, no copy); the
+    head and an attached FlightRecorder read that row.  It is what gym_fixed_wing.monitor.EpisodeMonitor folds.  The one-launch
+    step reads the previous reward and writes the new one through ONE pointer (reward_io), so it cannot do this: fused=True is
+    refused and None / "auto" take the two-launch path."""
+
+    def __init__(self, vec, actor, n_steps, graph=False, fused=None, tap=None, raw_rewards=False):
         self.vec, self.actor, self.n_steps = vec, actor, int(n_steps)
         m, N, D, A = vec._mem, vec.num_envs, vec.obs_dim, actor.act_dim
         self.buf = {"obs": m.zeros((n_steps, N, D)), "actions": m.zeros((n_steps, N, A)), "values": m.zeros((n_steps, N)),
                     "logp": m.zeros((n_steps, N)), "rewards": m.zeros((n_steps, N)), "dones": m.zeros((n_steps, N), "u8")}
+        self.raw_rewards = bool(raw_rewards)
+        self.warmup = None   # graph=True with raw_rewards: (raw_rewards [2, N], dones [2, N]) of the capture's two warm-up steps
+        if self.raw_rewards:
+            self.buf["raw_rewards"] = m.zeros((n_steps, N))
         # the head's outputs for the CURRENT observation, carried from one rollout to the next
         self.cur = {"obs": m.zeros((N, D)), "actions": m.zeros((N, A)), "values": m.zeros((N,)), "logp": m.zeros((N,))}
         self.last_value = self.cur["values"]
@@ -250,6 +260,10 @@ class FusedRollout(object):
         # a FlightRecorder (gym_fixed_wing.recorder) records behind every fwg_step launch: the one-launch step has no such
         # boundary, so "auto" / None take the two-launch path with a recorder attached and fused=True is refused
         recording = getattr(vec, "_recorder", None) is not None
+        if self.raw_rewards and fused and fused != "auto":
+            raise ValueError("FusedRollout(fused=True, raw_rewards=True): the one-launch step (fwg_rollout_step) keeps the reward in "
+                             "one in-out buffer and cannot write rollout rows -- use the two-launch path (fused=False, None or 'auto')")
+        recording = recording or self.raw_rewards   # (either way: the two-launch path)
         if fused == "auto":   # the one-launch step wherever it is available
             fused = bool(can_fuse) and not recording
         if fused and recording:
@@ -276,10 +290,12 @@ class FusedRollout(object):
             self.actor.act(o, norm_obs=c["obs"], action=c["actions"], value=c["values"], logp=c["logp"])
             self._primed = True
 
-    def _step(self, action, nxt, reward_out=None, done_out=None):
-        """One env step under `action`, then the head on the new observation writing into the slices of `nxt`."""
+    def _step(self, action, nxt, reward_out=None, done_out=None, raw_out=None):
+        """One env step under `action`, then the head on the new observation writing into the slices of `nxt`.  raw_out: where
+        the env step writes its rewards (default: the env's own buffer)."""
         vec, actor = self.vec, self.actor
-        o, r, d = vec.step_device(action, want_obs=self._attached)
+        # (without raw_out the call is the one it always was)
+        o, r, d = vec.step_device(action, want_obs=self._attached, **({} if raw_out is None else {"reward_out": raw_out}))
         if not self._attached:
             o = vec._obs_buf    # the row log itself: the head windows it on the device
             actor.observe(o, r, d)
@@ -307,9 +323,10 @@ class FusedRollout(object):
             return
         for t in range(n):
             nxt = cur if t == n - 1 else {k: buf[k][t + 1] for k in cur}
-            self._step(buf["actions"][t], nxt, buf["rewards"][t], buf["dones"][t])
+            raw = buf["raw_rewards"][t] if self.raw_rewards else None
+            self._step(buf["actions"][t], nxt, buf["rewards"][t], buf["dones"][t], raw)
             if tap is not None:
-                tap(t, self.vec._obs, self.vec._rew, self.vec._done)
+                tap(t, self.vec._obs, self.vec._rew if raw is None else raw, self.vec._done)
 
     def _capture(self):
         import torch
@@ -327,8 +344,11 @@ class FusedRollout(object):
                 o, r, d = self.actor.rollout_step(vec, norm_obs=c["obs"], action=c["actions"], value=c["values"], logp=c["logp"])
                 self.actor.act(o, reward=r, done=d, norm_obs=c["obs"], action=c["actions"], value=c["values"], logp=c["logp"])
             else:
-                self._step(self.cur["actions"], self.cur)
-                self._step(self.cur["actions"], self.cur)
+                # (the two warm-up steps are env steps like any other: with raw_rewards their rewards and done flags are kept in
+                # `warmup`, for the caller to fold before the first rollout -- otherwise every env's open episode would lose them)
+                warm = self.warmup = (vec._mem.zeros((2, vec.num_envs)), vec._mem.zeros((2, vec.num_envs), "u8")) if self.raw_rewards else None
+                for i in range(2):
+                    self._step(self.cur["actions"], self.cur, None, warm[1][i] if warm else None, warm[0][i] if warm else None)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()

@@ -213,6 +213,7 @@ class FixedWingVecEnv(object):
         self.check_actions = False
         self._pending = None
         self._recorder = None   # a gym_fixed_wing.recorder.FlightRecorder attaches itself here: one more launch per reset / step
+        self._monitor = None    # a gym_fixed_wing.monitor.EpisodeMonitor attaches itself here: reset() abandons its open episodes
         self.seed(seed)
 
     def _row_log_applies(self):
@@ -384,6 +385,8 @@ class FixedWingVecEnv(object):
                                                  m.ptr(tg) if tg is not None else null, m.ptr(self._obs_buf), m.stream()))
         if self._recorder is not None:
             self._recorder._on_reset(mask_t)
+        if self._monitor is not None:
+            self._monitor.reset(idx)
         self._refresh_obs_view()
         if st is not None or tg is not None or mask_t is not None:
             m.sync()  # the temporaries above must outlive the launch
@@ -442,23 +445,38 @@ class FixedWingVecEnv(object):
         self.step_async(actions)
         return self.step_wait()
 
-    def step_device(self, actions, want_obs=True, target_out=False):
+    def step_device(self, actions, want_obs=True, target_out=False, reward_out=None):
         """Fast path for on-device rollouts: no info objects; returns the (obs, reward, done) device tensors.
         `actions`: float32, contiguous, [N, 3], on this env's device.  want_obs=False (row-log mode): the caller reads
         the observation out of the log itself (the HIP rollout head does, fwg_actor_set_obs_log), so no view/gather.
         target_out=True: the step also writes info["target"] into self._target, as step() does (the device evaluation loop:
-        the PID baseline follows it)."""
+        the PID baseline follows it).  reward_out: a float32 contiguous [N] buffer on this env's device that receives the
+        step's rewards INSTEAD of self._rew (a row of FusedRollout's raw_rewards); it is what the call returns as the reward."""
         m = self._mem
         actions = self._checked_actions(actions)
-        nat.check(self._lib, self._lib.fwg_step(self._handle, m.ptr(actions), m.ptr(self._obs_buf), m.ptr(self._rew), m.ptr(self._done),
+        rew = self._rew if reward_out is None else self._checked_reward_out(reward_out)
+        nat.check(self._lib, self._lib.fwg_step(self._handle, m.ptr(actions), m.ptr(self._obs_buf), m.ptr(rew), m.ptr(self._done),
                                                 m.ptr(self._term), m.ptr(self._term_obs), m.ptr(self._metrics),
                                                 m.ptr(self._target) if target_out else ctypes.c_void_p(),   # (default: targets stay in the state arena)
                                                 m.stream()))
         if self._recorder is not None:
-            self._recorder._on_step(actions)
+            self._recorder._on_step(actions, rew)
         if want_obs:
             self._refresh_obs_view()
-        return self._obs, self._rew, self._done
+        return self._obs, rew, self._done
+
+    def _checked_reward_out(self, reward_out):
+        """As _checked_actions: the step kernel writes N floats through the raw pointer."""
+        t = reward_out
+        shape = tuple(getattr(t, "shape", ()))
+        ok = shape == (self.num_envs,) and str(t.dtype).endswith("float32")
+        if ok and hasattr(t, "is_contiguous"):
+            ok = t.is_contiguous() and t.device == self._rew.device
+        elif ok:
+            ok = bool(t.flags["C_CONTIGUOUS"])
+        if not ok:
+            raise ValueError("step_device: reward_out must be a float32 contiguous [{}] buffer on this env's device".format(self.num_envs))
+        return t
 
     def _checked_actions(self, actions):
         """step_device hands the raw pointer to the kernel: anything but a float32 contiguous [N, 3] batch on this device

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define FWG_ABI_VERSION 25
+#define FWG_ABI_VERSION 26
 
 #define FWG_N_VARS 23        /* simulator variables, see fwg_var */
 #define FWG_N_RESET_VARS 21  /* the keys of reset(state=...) records (fixed_wing.py:287,308; test-set format) */
@@ -42,6 +42,7 @@ extern "C" {
 #define FWG_N_DRYDEN 8       /* Dryden filter states (joint realisation u | v,r | w,q | p) */
 #define FWG_N_METRICS 28     /* rows of the metrics block written by fwg_step, see fwg_metric_row */
 #define FWG_N_REDUCE 16      /* floats accumulated for fwg_reduce_success */
+#define FWG_N_MONITOR 8      /* doubles written by fwg_monitor_take */
 
 typedef enum fwg_status {
     FWG_OK = 0,
@@ -673,6 +674,38 @@ int fwg_record_start(const fwg_handle* h, const int64_t* ids_dev, int n_tracked,
  * Both: FWG_ERR_INVALID for NULL buffers, n_tracked outside 1 .. 64, max_rows < 2. */
 int fwg_record(const fwg_handle* h, const int64_t* ids_dev, int n_tracked, const float* actions, const float* reward,
                const uint8_t* done, const uint8_t* term_code, float* rows, int32_t* hdr, int64_t max_rows, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Training monitor (ABI 26): the undiscounted return and the length of every episode that ends during a rollout -- the `r`
+ * and `l` that stable-baselines' Monitor wrapper attaches to an episode's last info and PPO2 logs as ep_rewmean / eplenmean
+ * (the first job of the reference's training callback, examples/train_rl_controller.py monitor_training).  The raw reward of
+ * step t is written by fwg_step itself when the caller passes row t of a [T][N] buffer as reward_out; fwg_monitor_fold folds
+ * that buffer and the rollout's done flags once per rollout.  Both calls are stateless like fwg_gae: caller-owned device
+ * buffers, one launch on `stream`, no allocation, no synchronisation.
+ *   raw_rewards : float32 [T][N]       dones : uint8 [T][N]       (step-major, as the rollout stores them)
+ *   ep_q_io     : int64 [N]            the open episode's return in units of 2^-20, carried from fold to fold (zero to start)
+ *   ep_len_io   : int32 [N]            its length so far; bit 31: it holds a bad reward
+ *   scratch     : fwg_monitor_scratch_bytes(N) bytes = [ceil(N / 64)][8] int64, ZEROED before the first fold (all-zero is the
+ *                 identity); one slot per workgroup, updated with plain loads and stores, so folds and takes on one scratch
+ *                 must be ordered (one stream)
+ * Per env, in step order:
+ *   q_t = (int64) rintf(r_t * 1048576.f)          (the product is exact in float; ties round to even)
+ *   r_t is BAD when !(fabsf(r_t) <= 1048576.f)    (NaN, inf, out of the bound)
+ *   good: ep_q += q_t;  bad: bit 31 of ep_len is set;  both: ep_len += 1
+ *   dones[t][e] != 0: the episode is emitted WITH the reward of step t, then (ep_q, ep_len) = (0, 0).  A flagged episode adds 1
+ *   to `nonfinite` and nothing else; any other updates episodes, sum_q, sum_len, min_q, max_q, min_len, max_len.
+ * Bounds: |r_t| <= 2^20 and steps_max < 65 535, so |ep_q| < 2^56.  All sums are integers: the result is independent of the
+ * kernel's split over time, of wave order and of how envs are sharded over ranks (bit for bit); the quantisation costs at most
+ * 2^-21 per step.  Several folds before one take accumulate.
+ * fwg_monitor_take writes FWG_N_MONITOR doubles to `out` (device): 0 episodes, 1 nonfinite, 2 sum_return = sum_q / 2^20,
+ * 3 sum_length, 4 min_return, 5 max_return, 6 min_length, 7 max_length (with no episode the minima are +inf and the maxima
+ * -inf), and resets the scratch to the identity.
+ * Both: FWG_ERR_INVALID for a NULL buffer, n_steps < 1, n_envs < 1 (nothing is launched).
+ * ------------------------------------------------------------------------------------------------------------------ */
+int64_t fwg_monitor_scratch_bytes(int64_t n_envs);   /* 0 for n_envs < 1 */
+int fwg_monitor_fold(int64_t n_steps, int64_t n_envs, const float* raw_rewards, const uint8_t* dones, int64_t* ep_q_io,
+                     int32_t* ep_len_io, void* scratch, void* stream);
+int fwg_monitor_take(int64_t n_envs, void* scratch, double* out, void* stream);
 
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);

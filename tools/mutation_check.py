@@ -7,7 +7,8 @@ tests/test_ppo_hip_contract.py (the ppo_cnn_* ones, slips in the backward pass t
 tests/test_ppo_hip_cnn.py).  The head mutants (head_*: the rollout head, fwgym_actor.h) likewise, against the emulated forms of
 tests/test_actor_contract.py (the head_cnn_* ones, slips in the CNN head's own code, those of tests/test_actor_contract_cnn.py); they are
 built for the host emulation only.  The eval_* mutants (the evaluation protocol on the device,
-fwgym_eval.h) run tests/test_eval_device.py; the recorder_* mutants (the device flight recorder, fwgym_record.h) tests/test_recorder.py.
+fwgym_eval.h) run tests/test_eval_device.py; the recorder_* mutants (the device flight recorder, fwgym_record.h) tests/test_recorder.py;
+the monitor_* mutants (the device training monitor, fwgym_monitor.h) the kernel tests of tests/test_monitor.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
@@ -160,6 +161,20 @@ MUTANTS = {
     # store_derived off in turbulence: Va read where store_derived would keep it (a word the step does not write then)
     "recorder_turbulent_va_from_the_first_group": [
         ("fwgym_record.h", "return rec_arena(S, N, e, rc.derived + (i == 3 ? 6 : i));", "return rec_arena(S, N, e, rc.derived + i);")],
+    # ---- the device training monitor (fwgym_monitor.h); they run the emulated forms, tests/test_monitor.py.
+    # a done inside a segment emits the episode but leaves the running sums where they are
+    "monitor_carry_not_cleared_at_a_done": [
+        ("fwgym_monitor.h", "                    q = 0; len = 0;\n                }\n", "                }\n")],
+    # the reward of the step that ends an episode goes to the next one
+    "monitor_done_reward_to_the_next_episode": [
+        ("fwgym_monitor.h", "                q += qk;\n", "                if (!d[k]) q += qk;\n"),
+        ("fwgym_monitor.h", "                    q = 0; len = 0;\n                }\n", "                    q = qk; len = 0;\n                }\n")],
+    # the lanes past the last env (they load env N - 1's values) emit its episodes once more
+    "monitor_lanes_past_n_counted": [
+        ("fwgym_monitor.h", "                if (d[k] && valid) {", "                if (d[k]) {")],
+    # the bad flag of an episode stays set in the episode that follows it
+    "monitor_bad_flag_survives_the_done": [
+        ("fwgym_monitor.h", "                    q = 0; len = 0;\n                }\n", "                    q = 0; len &= FWG_MON_BAD;\n                }\n")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -171,8 +186,9 @@ _HEAD_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract
 _CNN_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip_cnn.py")]
 _EVAL_TESTS = [os.path.join(ROOT, "tests", "test_eval_device.py")]
 _RECORDER_TESTS = [os.path.join(ROOT, "tests", "test_recorder.py")]
+_MONITOR_TESTS = ["-k", "restatement or bad_reward or carries or sharded", os.path.join(ROOT, "tests", "test_monitor.py")]
 _HEAD_CNN_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract_cnn.py")]
-TESTS = {name: (_RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+TESTS = {name: (_MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
