@@ -21,6 +21,7 @@
 #include "fwgym_learner.h" // the PPO update on the device (fwg_ppo_*)
 #include "fwgym_eval.h"    // the evaluation protocol on the device (fwg_pid_act, fwg_eval_advance)
 #include "fwgym_record.h"  // the device flight recorder (fwg_record_start, fwg_record)
+#include "fwgym_goal.h"    // the goal-conditioned view and hindsight relabelling (fwg_goal_observe, fwg_goal_reward, fwg_goal_relabel)
 #include "fwgym_monitor.h" // the device training monitor (fwg_monitor_fold, fwg_monitor_take)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
@@ -2365,6 +2366,134 @@ int fwg_record(const fwg_handle* h, const int64_t* ids_dev, int n_tracked, const
     if (!actions || !reward || !done || !term_code) return fail_with(FWG_ERR_INVALID, "fwg_record: null argument");
     hipLaunchKernelGGL(k_record, dim3((unsigned)n_tracked), dim3(64), 0, (hipStream_t)stream, rc, (const float*)h->arena, (long)h->n_envs,
                        (const long long*)ids_dev, n_tracked, actions, reward, done, term_code, rows, (int*)hdr, (long)max_rows);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+// ---- goal env (include/fwgym.h "Goal env"; kernels: fwgym_goal.h)
+static const char* goal_factor_words(const DevFactor& F) {
+    static const char* const cls[] = {"state", "action", "success", "step", "goal"};
+    static const char* const type[] = {"value", "error", "delta", "bound", "per_state", "all", "int_error"};
+    static thread_local std::string s;
+    s = std::string(F.cls >= 0 && F.cls < 5 ? cls[F.cls] : "?") + " / " + (F.type >= 0 && F.type < 7 ? type[F.type] : "?");
+    return s.c_str();
+}
+
+static int goal_window_of(const DevCfg& c) {
+    int W = 1;
+    for (int f = 0; f < c.n_factors; ++f)
+        if (c.factor[f].cls == FWG_RC_ACTION && c.factor[f].type == FWG_RT_DELTA && c.factor[f].window > W) W = c.factor[f].window;
+    return W < FWG_MAX_WINDOW ? W : FWG_MAX_WINDOW;
+}
+
+// the caller's spec against the handle's configuration -> what the kernels take by value; every refusal names its cause.
+// need_reward: the launch evaluates the reward function; relabel: the goal must also be constant within an episode
+static int goal_lower(const char* who, const fwg_handle* h, const fwg_goal_spec* spec, bool need_reward, bool relabel, GoalCfg* g) {
+    const std::string me(who);
+    if (!h || !spec) return fail_with(FWG_ERR_INVALID, me + ": null argument");
+    const DevCfg& c = h->h;
+    if (spec->n_goals < 1 || spec->n_goals > 3) return fail_with(FWG_ERR_INVALID, me + ": n_goals must be 1 .. 3");
+    if (spec->step_count_mode != 0 && spec->step_count_mode != 1) return fail_with(FWG_ERR_INVALID, me + ": step_count_mode must be 0 (compute_reward's) or 1 (step()'s)");
+    *g = GoalCfg{};
+    g->n = spec->n_goals; g->mode = spec->step_count_mode; g->window = goal_window_of(c);
+    int slot_goal[3] = {-1, -1, -1};
+    for (int i = 0; i < spec->n_goals; ++i) {
+        const int k = spec->k[i];
+        if (k < 0 || k >= c.n_targets) return fail_with(FWG_ERR_INVALID, me + ": goal " + std::to_string(i) + " names target slot " + std::to_string(k) + ", the handle has " + std::to_string(c.n_targets) + " target states");
+        if (slot_goal[k] >= 0) return fail_with(FWG_ERR_INVALID, me + ": target slot " + std::to_string(k) + " is named by two goals");
+        const int var = c.target[k].var;
+        if (var != FWG_V_ROLL && var != FWG_V_PITCH && var != FWG_V_VA)
+            return fail_with(FWG_ERR_INVALID, me + ": goal " + std::to_string(i) + " is simulator variable " + std::to_string(var) + ": a goal must be roll, pitch or Va");
+        if (!(spec->var[i] != 0.f) || !std::isfinite(spec->var[i]) || !std::isfinite(spec->mean[i]))
+            return fail_with(FWG_ERR_INVALID, me + ": goal " + std::to_string(i) + " needs a finite mean and a finite non-zero var");
+        slot_goal[k] = i;
+        g->k[i] = k; g->di[i] = var == FWG_V_ROLL ? 0 : (var == FWG_V_PITCH ? 1 : 3);
+        g->mean[i] = spec->mean[i]; g->var[i] = spec->var[i];
+    }
+    for (int i = spec->n_goals; i < 3; ++i) g->var[i] = 1.f;
+    if (!need_reward) return FWG_OK;
+    if (c.randomize_scaling)
+        return fail_with(FWG_ERR_INVALID, me + ": reward.randomize_scaling draws the factor scalings per env and episode: the reward of a substituted goal is not defined by the transition alone");
+    bool shaped_bound = false;
+    for (int f = 0; f < c.n_factors; ++f) {
+        const DevFactor& F = c.factor[f];
+        const std::string name = "reward factor " + std::to_string(f) + " (" + goal_factor_words(F) + ")";
+        if (F.cls == FWG_RC_STATE && F.type == FWG_RT_INT_ERROR)
+            return fail_with(FWG_ERR_INVALID, me + ": " + name + " sums the errors of earlier steps, which a transition does not carry");
+        if (F.cls == FWG_RC_STATE && F.type == FWG_RT_VALUE) {
+            bool found = false;
+            for (int i = 0; i < g->n; ++i) found = found || c.target[g->k[i]].var == F.src;
+            if (!found) return fail_with(FWG_ERR_INVALID, me + ": " + name + " reads simulator variable " + std::to_string(F.src) + ", which is not a goal");
+        }
+        if (F.cls == FWG_RC_STATE && F.type == FWG_RT_ERROR && (F.src < 0 || F.src > 2 || slot_goal[F.src] < 0))
+            return fail_with(FWG_ERR_INVALID, me + ": " + name + " reads the error of target slot " + std::to_string(F.src) + ", which is not a goal");
+        if (F.cls == FWG_RC_ACTION && F.type == FWG_RT_DELTA) g->has_delta = 1;
+        if (F.cls == FWG_RC_ACTION && F.type == FWG_RT_BOUND && F.shaping) shaped_bound = true;
+        if (F.cls == FWG_RC_GOAL) {
+            for (int k = 0; k < c.n_targets; ++k)
+                if (c.target[k].has_bound && slot_goal[k] < 0)
+                    return fail_with(FWG_ERR_INVALID, me + ": " + name + " counts the bounded target slot " + std::to_string(k) + ", which is not a goal");
+        }
+    }
+    if (c.reward_potential && shaped_bound && g->window < 2)
+        return fail_with(FWG_ERR_INVALID, me + ": a shaping action-bound factor under the potential form needs the action before the transition, and no delta factor widens the window to it");
+    if (relabel) {
+        if (c.any_dynamic_target) return fail_with(FWG_ERR_INVALID, me + ": linear / sinusoidal targets move within an episode: a relabelled goal must be constant");
+        if (c.resample_every > 0) return fail_with(FWG_ERR_INVALID, me + ": target.resample_every > 0 changes the goal within an episode");
+        if (c.on_success == FWG_ON_SUCCESS_NEW) return fail_with(FWG_ERR_INVALID, me + ": target.on_success == \"new\" changes the goal within an episode");
+    }
+    return FWG_OK;
+}
+
+int fwg_goal_window(const fwg_handle* h) {
+    if (!h) return fail_with(FWG_ERR_INVALID, "fwg_goal_window: null argument");
+    return goal_window_of(h->h);
+}
+
+int fwg_goal_observe(const fwg_handle* h, const fwg_goal_spec* spec, float* achieved, float* desired, void* stream) {
+    GoalCfg g;
+    if (const int st = goal_lower("fwg_goal_observe", h, spec, false, false, &g)) return st;
+    if (!achieved || !desired) return fail_with(FWG_ERR_INVALID, "fwg_goal_observe: null argument");
+    const fwg_layout& L = h->h.L;
+    const RecCfg rc = {L.sim, L.cold, L.derived, L.gym, h->h.store_derived, h->h.turbulence, h->h.auto_reset};
+    hipLaunchKernelGGL(k_goal_observe, dim3((unsigned)((h->n_envs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rc, g, (const float*)h->arena,
+                       (long)h->n_envs, (float4*)achieved, (float4*)desired);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_goal_reward(const fwg_handle* h, const fwg_goal_spec* spec, int64_t m, const float* achieved, const float* desired, const float* prev,
+                    const float* act_win, const int32_t* step, float* reward_out, void* stream) {
+    GoalCfg g;
+    if (const int st = goal_lower("fwg_goal_reward", h, spec, true, false, &g)) return st;
+    if (!achieved || !desired || !act_win || !step || !reward_out) return fail_with(FWG_ERR_INVALID, "fwg_goal_reward: null argument");
+    if (m < 1) return fail_with(FWG_ERR_INVALID, "fwg_goal_reward: m must be positive");
+    if (h->h.reward_potential && !prev) return fail_with(FWG_ERR_INVALID, "fwg_goal_reward: the potential reward form needs `prev`, the goal rows before the transitions");
+    hipLaunchKernelGGL(k_goal_reward, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const DevCfg*)h->d_cfg, g, (long)m,
+                       (const float4*)achieved, (const float4*)desired, (const float4*)prev, (const float4*)act_win, (const int*)step, reward_out);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_goal_relabel(const fwg_handle* h, const fwg_goal_spec* spec, int64_t n_steps, const float* achieved, const float* desired, const float* actions,
+                     const float* raw_rewards, const uint8_t* dones, uint64_t seed, uint32_t serial, uint64_t p_scaled, float* desired_out,
+                     float* reward_out, int32_t* src_row_out, void* stream) {
+    GoalCfg g;
+    if (const int st = goal_lower("fwg_goal_relabel", h, spec, true, true, &g)) return st;
+    if (!achieved || !desired || !actions || !raw_rewards || !dones || !desired_out || !reward_out || !src_row_out)
+        return fail_with(FWG_ERR_INVALID, "fwg_goal_relabel: null argument");
+    if (n_steps < 1 || n_steps > 0x7ffffffe) return fail_with(FWG_ERR_INVALID, "fwg_goal_relabel: n_steps must be in 1 .. 2^31 - 2");
+    if ((n_steps * h->n_envs + 255) / 256 > 0x7fffffff) return fail_with(FWG_ERR_INVALID, "fwg_goal_relabel: n_steps x n_envs is beyond one grid");
+    if (p_scaled > (1ull << 32)) return fail_with(FWG_ERR_INVALID, "fwg_goal_relabel: p_scaled must be in 0 .. 2^32");
+    GoalRelabel A;
+    A.achieved = (const float4*)achieved; A.desired = (const float4*)desired; A.actions = actions; A.raw = raw_rewards; A.done = dones;
+    A.desired_out = (float4*)desired_out; A.reward_out = reward_out; A.src_out = (int*)src_row_out;
+    A.T = (long)n_steps; A.N = (long)h->n_envs;
+    A.env_base = (unsigned)h->env_base; A.serial = serial; A.seed_lo = (unsigned)seed; A.seed_hi = (unsigned)(seed >> 32);
+    A.p_scaled = p_scaled;
+    hipLaunchKernelGGL(k_goal_relabel, dim3((unsigned)((h->n_envs + 63) / 64)), dim3(256), 4 * 64 * sizeof(int), (hipStream_t)stream, g, A);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_goal_relabel_reward, dim3((unsigned)((A.T * A.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const DevCfg*)h->d_cfg, g, A);
     HIP_TRY(hipGetLastError());
     return FWG_OK;
 }

@@ -161,6 +161,15 @@ class PidGains(C.Structure):
 REC_WORDS, REC_HDR, REC_MAX_TRACKED = 32, 8, 64
 REC_SLAB, REC_OPEN, REC_OVERFLOW, REC_OVERFLOW_DONE, REC_INVALID = 1, 2, 4, 8, 16
 
+class GoalSpecStruct(C.Structure):
+    """fwg_goal_spec (include/fwgym.h "Goal env"): which target states are goals, their scaling, the delta factor's step counter."""
+    _fields_ = [("n_goals", C.c_int32), ("step_count_mode", C.c_int32), ("k", C.c_int32 * 3), ("pad_", C.c_int32),
+                ("mean", C.c_float * 3), ("var", C.c_float * 3), ("inv_var", C.c_float * 3), ("pad2_", C.c_float)]
+
+
+GOAL_KEPT, GOAL_TERMINAL, GOAL_NO_WINDOW = -1, -2, -3   # fwg_goal_relabel's src_row_out values below 0
+STREAM_GOAL = 10                                        # Philox stream of the relabelling draws
+
 PPO_NSTAT = 4   # loss sums appended to a gradient buffer (include/fwgym.h "PPO update")
 
 
@@ -214,6 +223,10 @@ PROTOTYPES = {
     "fwg_monitor_scratch_bytes": (_i64, [_i64]),
     "fwg_monitor_fold": (_int, [_i64, _i64] + [_vp] * 6),
     "fwg_monitor_take": (_int, [_i64, _vp, _vp, _vp]),
+    "fwg_goal_window": (_int, [_vp]),
+    "fwg_goal_observe": (_int, [_vp, C.POINTER(GoalSpecStruct), _vp, _vp, _vp]),
+    "fwg_goal_reward": (_int, [_vp, C.POINTER(GoalSpecStruct), _i64] + [_vp] * 7),
+    "fwg_goal_relabel": (_int, [_vp, C.POINTER(GoalSpecStruct), _i64] + [_vp] * 5 + [_u64, C.c_uint32, _u64] + [_vp] * 4),
     "fwg_selftest_philox": (_int, [_vp, _vp, _i64, _vp]),
     "fwg_actor_create": (_int, [_int, _i64, _int, _int, _f32, _f32, _f32, _f32, C.POINTER(_vp)]),
     "fwg_actor_destroy": (None, [_vp]),

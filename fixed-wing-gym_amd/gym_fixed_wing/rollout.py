@@ -232,14 +232,25 @@ class FusedRollout(object):
     row t INSTEAD of vec._rew (fwg_step's reward_out argument: the same bytes to another address, no extra launch, no copy); the
     head and an attached FlightRecorder read that row.  It is what gym_fixed_wing.monitor.EpisodeMonitor folds.  The one-launch
     step reads the previous reward and writes the new one through ONE pointer (reward_io), so it cannot do this: fused=True is
-    refused and None / "auto" take the two-launch path."""
+    refused and None / "auto" take the two-launch path.
 
-    def __init__(self, vec, actor, n_steps, graph=False, fused=None, tap=None, raw_rewards=False):
+    `goals=log` (a gym_fixed_wing.goal.GoalLog of this env and n_steps): one fwg_goal_observe launch writes the goal rows of the
+    log, row 0 at the start of every rollout body (right whatever came before: a reset, the capture's warm-up steps, the previous
+    rollout) and row t + 1 behind env step t, eagerly and under graph=True.  Needs raw_rewards=True (log.relabel reads them) and
+    the two-launch path, with the refusals of raw_rewards."""
+
+    def __init__(self, vec, actor, n_steps, graph=False, fused=None, tap=None, raw_rewards=False, goals=None):
         self.vec, self.actor, self.n_steps = vec, actor, int(n_steps)
         m, N, D, A = vec._mem, vec.num_envs, vec.obs_dim, actor.act_dim
         self.buf = {"obs": m.zeros((n_steps, N, D)), "actions": m.zeros((n_steps, N, A)), "values": m.zeros((n_steps, N)),
                     "logp": m.zeros((n_steps, N)), "rewards": m.zeros((n_steps, N)), "dones": m.zeros((n_steps, N), "u8")}
         self.raw_rewards = bool(raw_rewards)
+        self.goals = goals
+        if goals is not None:
+            if not self.raw_rewards:
+                raise ValueError("FusedRollout(goals=log): relabelling reads the raw reward of every step -- pass raw_rewards=True")
+            if goals.vec is not vec or goals.n_steps != self.n_steps:
+                raise ValueError("FusedRollout(goals=log): the GoalLog belongs to another env or another rollout length")
         self.warmup = None   # graph=True with raw_rewards: (raw_rewards [2, N], dones [2, N]) of the capture's two warm-up steps
         if self.raw_rewards:
             self.buf["raw_rewards"] = m.zeros((n_steps, N))
@@ -321,10 +332,15 @@ class FusedRollout(object):
             actor.act(o, reward=r, done=d, norm_obs=cur["obs"], action=cur["actions"], value=cur["values"], logp=cur["logp"],
                       norm_reward=buf["rewards"][n - 1], done_out=buf["dones"][n - 1])
             return
+        goals = self.goals
+        if goals is not None:
+            goals.observe(0)
         for t in range(n):
             nxt = cur if t == n - 1 else {k: buf[k][t + 1] for k in cur}
             raw = buf["raw_rewards"][t] if self.raw_rewards else None
             self._step(buf["actions"][t], nxt, buf["rewards"][t], buf["dones"][t], raw)
+            if goals is not None:
+                goals.observe(t + 1)
             if tap is not None:
                 tap(t, self.vec._obs, self.vec._rew if raw is None else raw, self.vec._done)
 

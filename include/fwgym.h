@@ -707,6 +707,77 @@ int fwg_monitor_fold(int64_t n_steps, int64_t n_envs, const float* raw_rewards, 
                      int32_t* ep_len_io, void* scratch, void* stream);
 int fwg_monitor_take(int64_t n_envs, void* scratch, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Goal env: the reference's FixedWingAircraftGoal (a gym.GoalEnv, fixed_wing.py:1165-1277) for a whole batch -- the goal views of
+ * a dict observation, compute_reward(achieved_goal, desired_goal, info) for substituted goals, and hindsight relabelling ("future"
+ * strategy) of one rollout.  The exports are additions to ABI 26: no struct or call that existed changes.  All launches are
+ * stateless: caller-owned device buffers, the caller's stream, no allocation, no synchronisation, no atomics, and nothing passed by
+ * value changes from step to step, so they may sit inside a captured sequence of fwg_step calls.
+ *
+ * GOAL ROWS are float32 [..][4] (16 bytes): words 0..2 the scaled goals (x - mean) / var in the spec's order, unused words 0;
+ * word 3 per buffer, below.
+ *
+ * fwg_goal_spec, a host struct passed by pointer: which target states are goals and how they are scaled.  A goal must be one of the
+ * handle's target states (its slot k in target.states) and one of roll / pitch / Va.  The reward description is NOT part of it:
+ * the kernels read the handle's lowered configuration in device memory, so fwg_update_config is seen by the next launch.
+ * step_count_mode selects the step counter the action-delta factor sees: 0 = compute_reward's (steps_count = info["step"]: the
+ * factor is off for transitions 0 and 1, the reference's behaviour), 1 = step()'s (off for transition 0 only: with the goals a
+ * transition really had the result is the reward the step gave).
+ *
+ * THE REWARD FUNCTION (both fwg_goal_reward and fwg_goal_relabel) is get_reward (fixed_wing.py:674-774) with success = False for
+ * the unscaled achieved goals as state values and the unscaled desired goals as targets: wrapped errors as in the step; function
+ * classes linear (with max), quadratic, exponential; forms absolute and potential (previous shaping values from `prev` with the
+ * action before, and -- the reference's quirk -- the same action list for its value and delta factors); action factors from the
+ * window of raw actions; goal-class factors from the substituted errors and the configured bounds; success-class factors 0; the
+ * step class its constant.  Refused with FWG_ERR_INVALID and a message naming the factor -- what cannot be defined from a
+ * transition alone: int_error factors, reward.randomize_scaling, a state / error / goal factor that names a state or a bounded
+ * target that is not a goal, a shaping action-bound factor under the potential form without a delta factor's window; and, for
+ * fwg_goal_relabel only, linear / sinusoidal targets, resample_every > 0, on_success == "new" (the goal must be constant within an
+ * episode).  A refusal launches nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fwg_goal_spec {
+    int32_t n_goals;           /* 1 .. 3 */
+    int32_t step_count_mode;   /* 0: compute_reward's counter, 1: step()'s */
+    int32_t k[3];              /* per goal: index into target.states */
+    int32_t pad_;
+    float mean[3], var[3];     /* observation.goals[i]: scaled = (x - mean) / var (the kernels divide, as the reference does) */
+    float inv_var[3];          /* 1 / var, for callers that scale on their own; the kernels do not read it */
+    float pad2_;
+} fwg_goal_spec;
+enum { FWG_GOAL_KEPT = -1, FWG_GOAL_TERMINAL = -2, FWG_GOAL_NO_WINDOW = -3 };   /* src_row_out values below 0 */
+/* W: the largest window_size of the configuration's action-delta factors, 1 when there is none (host function). */
+int fwg_goal_window(const fwg_handle* h);
+/* One lane per env.  achieved [N][4]: the goal states of the committed state -- bit-equal to (w - mean) / var of the flight
+ * recorder's words 16 / 17 / 19 -- and in word 3 the arena's step word (layout.gym + 3) as raw bits: its low 16 bits are the
+ * episode's transition count so far.  desired [N][4]: the current targets (layout.gym + 0..2), word 3 = 0.  After a done step under
+ * auto_reset both show the new episode (count 0). */
+int fwg_goal_observe(const fwg_handle* h, const fwg_goal_spec* spec, float* achieved, float* desired, void* stream);
+/* The batched compute_reward: one lane per transition, m transitions.
+ *   achieved, desired : [m][4] goal rows after the transition / the goals to evaluate against
+ *   prev              : [m][4] goal rows before the transition; may be NULL unless the reward form is potential
+ *   act_win           : [W][m][4] raw actions (a0 a1 a2 -), W = fwg_goal_window: row W - 1 the transition's own action, row W - 1 - j
+ *                       the one j steps before it in the same episode; rows older than step[i] actions back are never read as values
+ *   step              : int32 [m] index of the transition in its episode        reward_out : float32 [m] */
+int fwg_goal_reward(const fwg_handle* h, const fwg_goal_spec* spec, int64_t m, const float* achieved, const float* desired,
+                    const float* prev, const float* act_win, const int32_t* step, float* reward_out, void* stream);
+/* HER's "future" strategy over one rollout of the handle's N envs, step-major as FusedRollout keeps it:
+ *   achieved, desired : [T + 1][N][4] rows of fwg_goal_observe: row 0 before step 0, row t + 1 behind step t
+ *   actions [T][N][3], raw_rewards [T][N], dones uint8 [T][N]
+ *   desired_out [T][N][4], reward_out [T][N], src_row_out int32 [T][N]
+ * For transition (t, n), idx = low 16 bits of word 3 of achieved[t][n], W = fwg_goal_window:
+ *   dones[t][n]: src = -2 (under auto-reset the achieved goal after a terminal step is not in the buffer);
+ *   else, if the configuration has a delta factor and min(idx, W - 1) > t: src = -3 (the window reaches before row 0);
+ *   else R = the first t_e > t with dones[t_e][n], or T; b = philox4x32(env_id_base + n, serial, t, 10, seed_lo, seed_hi);
+ *        (uint64) b.y >= p_scaled: src = -1; otherwise src = r = t + 1 + (uint32)(((uint64) b.x * (uint64)(R - t)) >> 32), the new
+ *        goal is words 0..2 of achieved[r][n], reward_out = the reward function on achieved[t + 1][n], the new goal, prev =
+ *        achieved[t][n], the window actions[t - j][n], step = idx; desired_out = the new goal with word 3 = 0.
+ *   wherever src < 0: desired_out = desired[t][n] (word 3 = 0) and reward_out = raw_rewards[t][n], bit for bit.
+ * p_scaled in [0, 2^32]: 2^32 relabels every eligible transition.  Sharding envs over handles with their env_id_base gives the
+ * columns of the whole, bit for bit. */
+int fwg_goal_relabel(const fwg_handle* h, const fwg_goal_spec* spec, int64_t n_steps, const float* achieved, const float* desired,
+                     const float* actions, const float* raw_rewards, const uint8_t* dones, uint64_t seed, uint32_t serial,
+                     uint64_t p_scaled, float* desired_out, float* reward_out, int32_t* src_row_out, void* stream);
+
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);
 

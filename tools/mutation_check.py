@@ -8,7 +8,8 @@ tests/test_ppo_hip_cnn.py).  The head mutants (head_*: the rollout head, fwgym_a
 tests/test_actor_contract.py (the head_cnn_* ones, slips in the CNN head's own code, those of tests/test_actor_contract_cnn.py); they are
 built for the host emulation only.  The eval_* mutants (the evaluation protocol on the device,
 fwgym_eval.h) run tests/test_eval_device.py; the recorder_* mutants (the device flight recorder, fwgym_record.h) tests/test_recorder.py;
-the monitor_* mutants (the device training monitor, fwgym_monitor.h) the kernel tests of tests/test_monitor.py.
+the monitor_* mutants (the device training monitor, fwgym_monitor.h) the kernel tests of tests/test_monitor.py; the goal_* mutants
+(the goal env, fwgym_goal.h) the kernel tests of tests/test_goal.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
@@ -175,6 +176,17 @@ MUTANTS = {
     # the bad flag of an episode stays set in the episode that follows it
     "monitor_bad_flag_survives_the_done": [
         ("fwgym_monitor.h", "                    q = 0; len = 0;\n                }\n", "                    q = 0; len &= FWG_MON_BAD;\n                }\n")],
+    # ---- the goal env (fwgym_goal.h); they run the emulated forms, the kernel tests of tests/test_goal.py.
+    # the substituted error of an angle without the wrap
+    "goal_error_without_the_wrap": [
+        ("fwgym_goal.h", "err[k] = target_error(c.target[k], tgt[i], val[i]);", "err[k] = c.target[k].wrap ? val[i] - tgt[i] : tgt[i] - val[i];")],
+    # R one row too far: the future goal may come from the row behind the episode's last one, across a done
+    "goal_future_row_across_a_done": [
+        ("fwgym_goal.h", "            const long R = later != 0u ? t + __ffsll((long long)later) : after;",
+         "            const long R = min(T, (later != 0u ? t + (long)__ffsll((long long)later) : after) + 1);")],
+    # the action window of the delta factor not cut at the episode's first action
+    "goal_window_not_cut_at_the_episode_start": [
+        ("fwgym_goal.h", "                    const int m = (int)min(step + 1u, (unsigned)F.window);", "                    const int m = F.window;")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -187,8 +199,9 @@ _CNN_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip
 _EVAL_TESTS = [os.path.join(ROOT, "tests", "test_eval_device.py")]
 _RECORDER_TESTS = [os.path.join(ROOT, "tests", "test_recorder.py")]
 _MONITOR_TESTS = ["-k", "restatement or bad_reward or carries or sharded", os.path.join(ROOT, "tests", "test_monitor.py")]
+_GOAL_TESTS = ["-k", "matches_the_restatement or golden or own_goals or sharded", os.path.join(ROOT, "tests", "test_goal.py")]
 _HEAD_CNN_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract_cnn.py")]
-TESTS = {name: (_MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+TESTS = {name: (_GOAL_TESTS if name.startswith("goal_") else _MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
