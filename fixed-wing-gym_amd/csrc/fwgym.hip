@@ -22,6 +22,7 @@
 #include "fwgym_eval.h"    // the evaluation protocol on the device (fwg_pid_act, fwg_eval_advance)
 #include "fwgym_record.h"  // the device flight recorder (fwg_record_start, fwg_record)
 #include "fwgym_goal.h"    // the goal-conditioned view and hindsight relabelling (fwg_goal_observe, fwg_goal_reward, fwg_goal_relabel)
+#include "fwgym_replay.h"  // the hindsight replay buffer: episode index and relabelling at sample time (fwg_replay_index, fwg_replay_sample)
 #include "fwgym_monitor.h" // the device training monitor (fwg_monitor_fold, fwg_monitor_take)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
@@ -2494,6 +2495,54 @@ int fwg_goal_relabel(const fwg_handle* h, const fwg_goal_spec* spec, int64_t n_s
     hipLaunchKernelGGL(k_goal_relabel, dim3((unsigned)((h->n_envs + 63) / 64)), dim3(256), 4 * 64 * sizeof(int), (hipStream_t)stream, g, A);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_goal_relabel_reward, dim3((unsigned)((A.T * A.N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const DevCfg*)h->d_cfg, g, A);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+// ---- hindsight replay (include/fwgym.h "Hindsight replay"; kernels: fwgym_replay.h)
+int fwg_replay_index(int64_t n_steps, int64_t n_envs, const uint8_t* dones, int32_t* ep_end, void* stream) {
+    if (!dones || !ep_end) return fail_with(FWG_ERR_INVALID, "fwg_replay_index: null argument");
+    if (n_steps < 1 || n_steps > 0x7ffffffe) return fail_with(FWG_ERR_INVALID, "fwg_replay_index: n_steps must be in 1 .. 2^31 - 2");
+    if (n_envs < 1 || (n_envs + 63) / 64 > 0x7fffffff) return fail_with(FWG_ERR_INVALID, "fwg_replay_index: n_envs must be positive and within one grid");
+    hipLaunchKernelGGL(k_replay_index, dim3((unsigned)((n_envs + 63) / 64)), dim3(256), 4 * 64 * sizeof(int), (hipStream_t)stream, (long)n_steps, (long)n_envs,
+                       (const unsigned char*)dones, (int*)ep_end);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+int fwg_replay_sample(const fwg_handle* h, const fwg_goal_spec* spec, const fwg_replay_view* view, int strategy, int64_t batch, uint64_t seed,
+                      uint32_t serial, uint64_t p_scaled, float* obs_out, float* next_obs_out, float* action_out, float* achieved_out,
+                      float* desired_out, float* reward_out, uint8_t* done_out, int32_t* index_out, void* stream) {
+    GoalCfg g;
+    if (const int st = goal_lower("fwg_replay_sample", h, spec, true, true, &g)) return st;
+    if (!view) return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: null argument");
+    const fwg_replay_view& v = *view;
+    if (!v.obs || !v.actions || !v.raw_rewards || !v.dones || !v.ep_end || !v.achieved || !v.desired || !obs_out || !next_obs_out || !action_out ||
+        !achieved_out || !desired_out || !reward_out || !done_out || !index_out)
+        return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: null argument");
+    if (v.n_steps < 1 || v.n_steps > 0x7ffffffe) return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: n_steps must be in 1 .. 2^31 - 2");
+    if (v.n_envs != h->n_envs) return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: the view holds " + std::to_string(v.n_envs) + " envs, the handle " + std::to_string(h->n_envs));
+    if (v.n_slots < 1 || v.n_slots > 0x7fffffff) return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: n_slots must be in 1 .. 2^31 - 1");
+    if (v.n_filled < 1 || v.n_filled > v.n_slots)
+        return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: n_filled must be in 1 .. n_slots (" + std::to_string(v.n_slots) + "), it is " + std::to_string(v.n_filled) + ": nothing is stored");
+    if (v.obs_words < 1 || v.obs_words > FWG_REPLAY_MAX_OBS) return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: obs_words must be in 1 .. " + std::to_string(FWG_REPLAY_MAX_OBS));
+    if (strategy != FWG_REPLAY_FUTURE && strategy != FWG_REPLAY_FINAL && strategy != FWG_REPLAY_EPISODE)
+        return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: unknown strategy " + std::to_string(strategy) + " (0 future, 1 final, 2 episode)");
+    if (batch < 1 || batch > 0xffffffffll) return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: the batch must be in 1 .. 2^32 - 1");
+    if (p_scaled > (1ull << 32)) return fail_with(FWG_ERR_INVALID, "fwg_replay_sample: p_scaled must be in 0 .. 2^32");
+    ReplaySample A;
+    A.obs = v.obs; A.actions = v.actions; A.raw = v.raw_rewards; A.done = v.dones; A.ep_end = (const int*)v.ep_end;
+    A.achieved = (const float4*)v.achieved; A.desired = (const float4*)v.desired;
+    A.obs_out = obs_out; A.next_obs_out = next_obs_out; A.action_out = action_out; A.achieved_out = (float4*)achieved_out;
+    A.desired_out = (float4*)desired_out; A.reward_out = reward_out; A.done_out = done_out; A.index_out = (int*)index_out;
+    A.T = (long)v.n_steps; A.N = (long)v.n_envs; A.B = (long)batch;
+    A.D = v.obs_words; A.strategy = strategy;
+    A.vec4 = (v.obs_words % 4 == 0) && (((uintptr_t)v.obs | (uintptr_t)obs_out | (uintptr_t)next_obs_out) % 16 == 0);
+    A.n_slots = (unsigned)v.n_slots; A.n_filled = (unsigned)v.n_filled;
+    A.serial = serial; A.seed_lo = (unsigned)seed; A.seed_hi = (unsigned)(seed >> 32);
+    A.p_scaled = p_scaled;
+    hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)((batch + FWG_REPLAY_BLOCK - 1) / FWG_REPLAY_BLOCK)), dim3(FWG_REPLAY_BLOCK),
+                       FWG_REPLAY_BLOCK * sizeof(long), (hipStream_t)stream, (const DevCfg*)h->d_cfg, g, A);
     HIP_TRY(hipGetLastError());
     return FWG_OK;
 }

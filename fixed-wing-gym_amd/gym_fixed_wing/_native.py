@@ -170,6 +170,17 @@ class GoalSpecStruct(C.Structure):
 GOAL_KEPT, GOAL_TERMINAL, GOAL_NO_WINDOW = -1, -2, -3   # fwg_goal_relabel's src_row_out values below 0
 STREAM_GOAL = 10                                        # Philox stream of the relabelling draws
 
+class ReplayView(C.Structure):
+    """fwg_replay_view (include/fwgym.h "Hindsight replay"): the sizes and the slot-major device buffers of a replay buffer."""
+    _fields_ = [("n_slots", C.c_int64), ("n_filled", C.c_int64), ("n_steps", C.c_int64), ("n_envs", C.c_int64),
+                ("obs_words", C.c_int32), ("pad_", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ["obs", "actions", "raw_rewards", "dones", "ep_end", "achieved", "desired"]]
+
+
+REPLAY_STRATEGIES = {"future": 0, "final": 1, "episode": 2}   # FWG_REPLAY_FUTURE / _FINAL / _EPISODE
+REPLAY_MAX_OBS = 240                                            # FWG_REPLAY_MAX_OBS
+STREAM_REPLAY = 11                                              # Philox stream of the replay draws
+
 PPO_NSTAT = 4   # loss sums appended to a gradient buffer (include/fwgym.h "PPO update")
 
 
@@ -227,6 +238,8 @@ PROTOTYPES = {
     "fwg_goal_observe": (_int, [_vp, C.POINTER(GoalSpecStruct), _vp, _vp, _vp]),
     "fwg_goal_reward": (_int, [_vp, C.POINTER(GoalSpecStruct), _i64] + [_vp] * 7),
     "fwg_goal_relabel": (_int, [_vp, C.POINTER(GoalSpecStruct), _i64] + [_vp] * 5 + [_u64, C.c_uint32, _u64] + [_vp] * 4),
+    "fwg_replay_index": (_int, [_i64, _i64, _vp, _vp, _vp]),
+    "fwg_replay_sample": (_int, [_vp, C.POINTER(GoalSpecStruct), C.POINTER(ReplayView), _int, _i64, _u64, C.c_uint32, _u64] + [_vp] * 9),
     "fwg_selftest_philox": (_int, [_vp, _vp, _i64, _vp]),
     "fwg_actor_create": (_int, [_int, _i64, _int, _int, _f32, _f32, _f32, _f32, C.POINTER(_vp)]),
     "fwg_actor_destroy": (None, [_vp]),

@@ -778,6 +778,67 @@ int fwg_goal_relabel(const fwg_handle* h, const fwg_goal_spec* spec, int64_t n_s
                      const float* actions, const float* raw_rewards, const uint8_t* dones, uint64_t seed, uint32_t serial,
                      uint64_t p_scaled, float* desired_out, float* reward_out, int32_t* src_row_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Hindsight replay: what an off-policy learner puts between a goal env and its update -- many rollouts kept on the device
+ * ("slots"), minibatches drawn uniformly over all of them, and a fresh hindsight goal with that goal's reward every time a
+ * transition is drawn (fwg_goal_relabel relabels one rollout once, in place).  The exports are additions to ABI 26: no struct or
+ * call that existed changes.  Both launches are stateless: caller-owned device buffers, the caller's stream, no allocation, no
+ * synchronisation, no atomics.  A refusal launches nothing and returns FWG_ERR_INVALID with a message.
+ *
+ * fwg_replay_index, once per stored rollout (it needs no handle): dones uint8 [T][N] -> ep_end int32 [T][N],
+ *   ep_end[t][n] = the first t_e > t with dones[t_e][n], or T when there is none (the R of fwg_goal_relabel).
+ * Refused: a NULL buffer, n_steps outside 1 .. 2^31 - 2, n_envs < 1.
+ *
+ * fwg_replay_view, a host struct passed by pointer: the slots.  Slot-major device buffers, K = n_slots of them allocated and the
+ * first n_filled holding rollouts of the handle's N envs over T steps:
+ *   obs [K][T + 1][N][D] (row t the observation before step t, row T the one behind the last step; D = obs_words, 1 .. 240)
+ *   actions [K][T][N][3], raw_rewards [K][T][N], dones uint8 [K][T][N], ep_end int32 [K][T][N] (fwg_replay_index per slot)
+ *   achieved, desired [K][T + 1][N][4]: the goal rows of fwg_goal_observe -- row 0 before step 0, row t + 1 behind step t, the step
+ *   word in word 3 of achieved.
+ *
+ * fwg_replay_sample draws `batch` transitions (1 .. 2^32 - 1).  With mulhi(x, m) = (uint32)(((uint64) x * m) >> 32), sample i is:
+ *   a = philox4x32(i, serial, 0, 11, seed_lo, seed_hi); slot k = mulhi(a.x, n_filled), t = mulhi(a.y, T), n = mulhi(a.z, N)
+ *       (uniform over the stored transitions, with replacement);
+ *   idx = low 16 bits of word 3 of achieved[k][t][n], W = fwg_goal_window, R = ep_end[k][t][n];
+ *   dones[k][t][n]: src = -2;
+ *   else, if the configuration has a delta factor and min(idx, W - 1) > t: src = -3 (the window reaches before row 0);
+ *   else, if (uint64) a.w >= p_scaled: src = -1;
+ *   else src = a row r of the same slot and episode, with b = philox4x32(i, serial, 1, 11, seed_lo, seed_hi):
+ *       FWG_REPLAY_FUTURE   r = t + 1 + mulhi(b.x, R - t)                      (a row behind the transition: t < r <= R)
+ *       FWG_REPLAY_FINAL    r = R                                              (the last row of the episode the slot holds)
+ *       FWG_REPLAY_EPISODE  s0 = max(t - idx, 0), r = s0 + 1 + mulhi(b.x, R - s0)   (any row of the episode: s0 < r <= R)
+ *     the goal never comes from outside the slot, nor from across a done;
+ *   src >= 0: the new goal is words 0..2 of achieved[k][r][n]; reward_out = the reward function (above, under
+ *       spec->step_count_mode) on achieved[k][t + 1][n], the new goal, prev = achieved[k][t][n], the window actions[k][t - j][n],
+ *       step = idx;
+ *   src < 0: the goal is desired[k][t][n] and reward_out = raw_rewards[k][t][n], bit for bit.
+ * Outputs, one row per sample: obs_out [B][D] = obs[k][t][n], next_obs_out [B][D] = obs[k][t + 1][n], action_out [B][3],
+ * achieved_out [B][4] = achieved[k][t + 1][n] and desired_out [B][4] the goal (word 3 = 0 in both), reward_out [B], done_out uint8
+ * [B] = dones[k][t][n], index_out int32 [B][4] = (k, t, n, src).
+ * UNDER AUTO-RESET the rows behind a terminal step show the NEXT episode: next_obs_out and achieved_out of a sample with done_out
+ * set are the first observation and goals of the episode that follows (the learner masks the bootstrap with done_out).
+ * Refused: what fwg_goal_relabel refuses (the configuration, NULL buffers, n_steps, p_scaled > 2^32), and a view of another N than
+ * the handle's, n_filled < 1 or > n_slots, an unknown strategy, obs_words outside 1 .. 240, batch outside 1 .. 2^32 - 1.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define FWG_REPLAY_MAX_OBS 240
+enum { FWG_REPLAY_FUTURE = 0, FWG_REPLAY_FINAL = 1, FWG_REPLAY_EPISODE = 2 };
+typedef struct fwg_replay_view {
+    int64_t n_slots, n_filled;   /* K allocated, 1 .. K of them hold a rollout */
+    int64_t n_steps, n_envs;     /* T; N, the handle's */
+    int32_t obs_words, pad_;     /* D */
+    const float* obs;
+    const float* actions;
+    const float* raw_rewards;
+    const uint8_t* dones;
+    const int32_t* ep_end;
+    const float* achieved;
+    const float* desired;
+} fwg_replay_view;
+int fwg_replay_index(int64_t n_steps, int64_t n_envs, const uint8_t* dones, int32_t* ep_end, void* stream);
+int fwg_replay_sample(const fwg_handle* h, const fwg_goal_spec* spec, const fwg_replay_view* view, int strategy, int64_t batch,
+                      uint64_t seed, uint32_t serial, uint64_t p_scaled, float* obs_out, float* next_obs_out, float* action_out,
+                      float* achieved_out, float* desired_out, float* reward_out, uint8_t* done_out, int32_t* index_out, void* stream);
+
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);
 

@@ -9,7 +9,8 @@ tests/test_actor_contract.py (the head_cnn_* ones, slips in the CNN head's own c
 built for the host emulation only.  The eval_* mutants (the evaluation protocol on the device,
 fwgym_eval.h) run tests/test_eval_device.py; the recorder_* mutants (the device flight recorder, fwgym_record.h) tests/test_recorder.py;
 the monitor_* mutants (the device training monitor, fwgym_monitor.h) the kernel tests of tests/test_monitor.py; the goal_* mutants
-(the goal env, fwgym_goal.h) the kernel tests of tests/test_goal.py.
+(the goal env, fwgym_goal.h) the kernel tests of tests/test_goal.py; the replay_* mutants (the hindsight replay buffer, fwgym_replay.h)
+the kernel tests of tests/test_replay.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
@@ -187,6 +188,14 @@ MUTANTS = {
     # the action window of the delta factor not cut at the episode's first action
     "goal_window_not_cut_at_the_episode_start": [
         ("fwgym_goal.h", "                    const int m = (int)min(step + 1u, (unsigned)F.window);", "                    const int m = F.window;")],
+    # ---- the hindsight replay buffer (fwgym_replay.h); they run the emulated forms, the kernel tests of tests/test_replay.py.
+    # a future row that may reach one row past R (capped at the slot's last row): the goal may come from across a done
+    "replay_future_row_past_the_episode": [
+        ("fwgym_replay.h", "            src = (int)(s0 + 1 + (long)__umulhi(b.x, (unsigned)(R - s0)));",
+         "            src = (int)min(T, s0 + 1 + (long)__umulhi(b.x, (unsigned)(R - s0 + 1)));")],
+    # the slot drawn over the K allocated slots instead of the n_filled that hold a rollout
+    "replay_slot_drawn_over_all_slots": [
+        ("fwgym_replay.h", "        const long k = (long)__umulhi(a.x, A.n_filled);", "        const long k = (long)__umulhi(a.x, A.n_slots);")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -199,9 +208,10 @@ _CNN_LEARNER_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_ppo_hip
 _EVAL_TESTS = [os.path.join(ROOT, "tests", "test_eval_device.py")]
 _RECORDER_TESTS = [os.path.join(ROOT, "tests", "test_recorder.py")]
 _MONITOR_TESTS = ["-k", "restatement or bad_reward or carries or sharded", os.path.join(ROOT, "tests", "test_monitor.py")]
+_REPLAY_TESTS = ["-k", "restatement or seed_and_serial or backward_scan", os.path.join(ROOT, "tests", "test_replay.py")]
 _GOAL_TESTS = ["-k", "matches_the_restatement or golden or own_goals or sharded", os.path.join(ROOT, "tests", "test_goal.py")]
 _HEAD_CNN_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract_cnn.py")]
-TESTS = {name: (_GOAL_TESTS if name.startswith("goal_") else _MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+TESTS = {name: (_REPLAY_TESTS if name.startswith("replay_") else _GOAL_TESTS if name.startswith("goal_") else _MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
