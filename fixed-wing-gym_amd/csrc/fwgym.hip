@@ -19,6 +19,7 @@
 #include "fwgym_env.h"
 #include "fwgym_actor.h"   // the rollout head (k_rollout below runs it in the same launch as the env step)
 #include "fwgym_learner.h" // the PPO update on the device (fwg_ppo_*)
+#include "fwgym_offpolicy.h" // the off-policy update on the device: DDPG with twin critics (fwg_ddpg_*)
 #include "fwgym_eval.h"    // the evaluation protocol on the device (fwg_pid_act, fwg_eval_advance)
 #include "fwgym_record.h"  // the device flight recorder (fwg_record_start, fwg_record)
 #include "fwgym_goal.h"    // the goal-conditioned view and hindsight relabelling (fwg_goal_observe, fwg_goal_reward, fwg_goal_relabel)
@@ -3216,6 +3217,146 @@ int fwg_actor_pack(fwg_learner* L, const float* params, void* stream) {
                        a->d_frags, a->d_bias, a->d_log_std);
     HIP_TRY(hipGetLastError());
     return FWG_OK;
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// Off-policy update (include/fwgym.h "Off-policy update"): kernels in fwgym_offpolicy.h
+// =====================================================================================================================
+struct fwg_offpolicy {
+    DdpgLayout L;
+    float* d_slab;     // [FWG_PPO_MAX_BLOCKS][SW] partial gradients of the two gradient launches
+    float* d_grad;     // [P + FWG_DDPG_NSTAT] flat gradient of fwg_ddpg_step
+};
+
+static const char* ddpg_batch_null(const fwg_offpolicy_batch* b) {   // the first null member's name
+    if (!b) return "batch";
+    if (!b->obs) return "batch.obs";
+    if (!b->next_obs) return "batch.next_obs";
+    if (!b->action) return "batch.action";
+    if (!b->goal_rows) return "batch.goal_rows";
+    if (!b->reward) return "batch.reward";
+    if (!b->done) return "batch.done";
+    return nullptr;
+}
+static DdpgHparams ddpg_hparams(const fwg_ddpg_hparams* hp) {
+    DdpgHparams H;
+    H.gamma = hp->gamma; H.tau = hp->tau; H.lr_actor = hp->lr_actor; H.lr_critic = hp->lr_critic; H.beta1 = hp->beta1; H.beta2 = hp->beta2;
+    H.eps = hp->eps; H.max_norm_actor = hp->max_grad_norm_actor; H.max_norm_critic = hp->max_grad_norm_critic;
+    return H;
+}
+// seg 1: k_ddpg_critic_grad, seg 0: k_ddpg_actor_grad; then the segment's slab reduction into grad_out
+static int ddpg_launch_grad(fwg_offpolicy* O, int seg, const fwg_offpolicy_batch* b, int64_t n, float gamma, const float* params, const float* target,
+                            float* grad_out, float* y_out, hipStream_t st) {
+    DdpgGradArgs G;
+    G.B.obs = b->obs; G.B.next_obs = b->next_obs; G.B.act = b->action; G.B.goal = b->goal_rows; G.B.rew = b->reward; G.B.done = b->done;
+    G.n = (long)n; G.ntiles = (long)((n + FWG_PPO_ROWS - 1) / FWG_PPO_ROWS);
+    G.params = params; G.target = target; G.gamma = gamma; G.slab = O->d_slab; G.y_out = y_out; G.L = O->L;
+    const unsigned nb = (unsigned)(G.ntiles < FWG_PPO_MAX_BLOCKS ? G.ntiles : FWG_PPO_MAX_BLOCKS);
+    if (seg) hipLaunchKernelGGL(k_ddpg_critic_grad, dim3(nb), dim3(FWG_PPO_THREADS), (size_t)ddpg_lds_floats(FWG_DDPG_TILES_CRITIC) * sizeof(float), st, G);
+    else hipLaunchKernelGGL(k_ddpg_actor_grad, dim3(nb), dim3(FWG_PPO_THREADS), (size_t)ddpg_lds_floats(FWG_DDPG_TILES_ACTOR) * sizeof(float), st, G);
+    HIP_TRY(hipGetLastError());
+    const int m = (seg ? O->L.P - O->L.PA : O->L.PA) + FWG_DDPG_NSTAT;
+    hipLaunchKernelGGL(k_ddpg_reduce, dim3((unsigned)((m + FWG_PPO_THREADS - 1) / FWG_PPO_THREADS)), dim3(FWG_PPO_THREADS), 0, st,
+                       (const float*)O->d_slab, (int)nb, O->L, seg, grad_out);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
+}
+
+extern "C" {
+
+int fwg_offpolicy_create(int obs_words, int goal_words, int act_dim, int n_critics, fwg_offpolicy** out) {
+    if (!out) return fail_with(FWG_ERR_INVALID, "fwg_offpolicy_create: out is null");
+    const std::string sizes = " (obs_words " + std::to_string(obs_words) + ", goal_words " + std::to_string(goal_words) + ", act_dim " + std::to_string(act_dim) + ")";
+    if (obs_words < 1) return fail_with(FWG_ERR_INVALID, "fwg_offpolicy_create: obs_words must be positive" + sizes);
+    if (goal_words < 1 || goal_words > 4) return fail_with(FWG_ERR_INVALID, "fwg_offpolicy_create: goal_words must be in 1 .. 4" + sizes);
+    if (act_dim < 1 || act_dim > FWG_ACT_MAX_ACT) return fail_with(FWG_ERR_INVALID, "fwg_offpolicy_create: act_dim must be in 1 .. 4" + sizes);
+    if (n_critics != 1 && n_critics != 2) return fail_with(FWG_ERR_INVALID, "fwg_offpolicy_create: n_critics must be 1 or 2, it is " + std::to_string(n_critics));
+    if ((long)obs_words + goal_words + act_dim > 64)
+        return fail_with(FWG_ERR_INVALID, "fwg_offpolicy_create: the critic's input width obs_words + goal_words + act_dim = " +
+                         std::to_string((long)obs_words + goal_words + act_dim) + " exceeds 64, one LDS tile row" + sizes);
+    fwg_offpolicy* O = new fwg_offpolicy();
+    O->L = ddpg_layout(obs_words, goal_words, act_dim, n_critics);
+    O->d_slab = nullptr; O->d_grad = nullptr;
+    const int rc = [&]() -> int {
+        HIP_TRY(hipMalloc((void**)&O->d_slab, (size_t)FWG_PPO_MAX_BLOCKS * O->L.SW * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&O->d_grad, (size_t)(O->L.P + FWG_DDPG_NSTAT) * sizeof(float)));
+        HIP_TRY(hipMemset(O->d_slab, 0, (size_t)FWG_PPO_MAX_BLOCKS * O->L.SW * sizeof(float)));
+        HIP_TRY(hipMemset(O->d_grad, 0, (size_t)(O->L.P + FWG_DDPG_NSTAT) * sizeof(float)));
+        // (more than 64 KiB of dynamic LDS)
+        HIP_TRY(hipFuncSetAttribute((const void*)k_ddpg_critic_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ddpg_lds_floats(FWG_DDPG_TILES_CRITIC) * sizeof(float))));
+        HIP_TRY(hipFuncSetAttribute((const void*)k_ddpg_actor_grad, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ddpg_lds_floats(FWG_DDPG_TILES_ACTOR) * sizeof(float))));
+        return FWG_OK;
+    }();
+    if (rc != FWG_OK) { fwg_offpolicy_destroy(O); return rc; }
+    *out = O;
+    return FWG_OK;
+}
+
+void fwg_offpolicy_destroy(fwg_offpolicy* O) {   // (also the failure exit of fwg_offpolicy_create: either buffer may still be null)
+    if (!O) return;
+    (void)hipFree(O->d_slab); (void)hipFree(O->d_grad);
+    delete O;
+}
+
+int64_t fwg_offpolicy_num_params(const fwg_offpolicy* O) { return O ? (int64_t)O->L.P : -1; }
+int64_t fwg_offpolicy_actor_params(const fwg_offpolicy* O) { return O ? (int64_t)O->L.PA : -1; }
+
+#define DDPG_NEED(fn, p) do { if (!(p)) return fail_with(FWG_ERR_INVALID, fn ": " #p " is null"); } while (0)
+#define DDPG_BATCH(fn, b, B) do { \
+        if (const char* nm_ = ddpg_batch_null(b)) return fail_with(FWG_ERR_INVALID, std::string(fn ": ") + nm_ + " is null"); \
+        if ((B) < 1) return fail_with(FWG_ERR_INVALID, fn ": B must be positive, it is " + std::to_string((long long)(B))); \
+    } while (0)
+
+int fwg_ddpg_critic_grad(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int64_t B, const fwg_ddpg_hparams* hparams, const float* params,
+                         const float* target_params, float* grad_out, float* td_target_out, void* stream) {
+    DDPG_NEED("fwg_ddpg_critic_grad", learner); DDPG_NEED("fwg_ddpg_critic_grad", hparams); DDPG_NEED("fwg_ddpg_critic_grad", params);
+    DDPG_NEED("fwg_ddpg_critic_grad", target_params); DDPG_NEED("fwg_ddpg_critic_grad", grad_out);
+    DDPG_BATCH("fwg_ddpg_critic_grad", batch, B);
+    return ddpg_launch_grad(learner, 1, batch, B, (float)hparams->gamma, params, target_params, grad_out, td_target_out, (hipStream_t)stream);
+}
+
+int fwg_ddpg_actor_grad(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int64_t B, const float* params, float* grad_out, void* stream) {
+    DDPG_NEED("fwg_ddpg_actor_grad", learner); DDPG_NEED("fwg_ddpg_actor_grad", params); DDPG_NEED("fwg_ddpg_actor_grad", grad_out);
+    DDPG_BATCH("fwg_ddpg_actor_grad", batch, B);
+    return ddpg_launch_grad(learner, 0, batch, B, 0.f, params, nullptr, grad_out, nullptr, (hipStream_t)stream);
+}
+
+int fwg_ddpg_apply(fwg_offpolicy* learner, int segment, const float* grad, int64_t B, const fwg_ddpg_hparams* hparams, float* params, float* adam_m,
+                   float* adam_v, int32_t* steps, float* stats_acc, float* target_params, void* stream) {
+    DDPG_NEED("fwg_ddpg_apply", learner); DDPG_NEED("fwg_ddpg_apply", grad); DDPG_NEED("fwg_ddpg_apply", hparams); DDPG_NEED("fwg_ddpg_apply", params);
+    DDPG_NEED("fwg_ddpg_apply", adam_m); DDPG_NEED("fwg_ddpg_apply", adam_v); DDPG_NEED("fwg_ddpg_apply", steps); DDPG_NEED("fwg_ddpg_apply", stats_acc);
+    if (segment != FWG_DDPG_ACTOR && segment != FWG_DDPG_CRITICS)
+        return fail_with(FWG_ERR_INVALID, "fwg_ddpg_apply: segment must be 0 (actor) or 1 (critics), it is " + std::to_string(segment));
+    if (B < 1) return fail_with(FWG_ERR_INVALID, "fwg_ddpg_apply: B must be positive, it is " + std::to_string((long long)B));
+    hipLaunchKernelGGL(k_ddpg_apply, dim3(1), dim3(FWG_PPO_APPLY_THREADS), FWG_PPO_APPLY_THREADS * sizeof(float), (hipStream_t)stream,
+                       grad, (long)B, learner->L, segment, ddpg_hparams(hparams), params, adam_m, adam_v, (int*)steps, stats_acc);
+    HIP_TRY(hipGetLastError());
+    if (target_params) {
+        const int P = learner->L.P;
+        hipLaunchKernelGGL(k_ddpg_polyak, dim3((unsigned)((P + FWG_PPO_THREADS - 1) / FWG_PPO_THREADS)), dim3(FWG_PPO_THREADS), 0, (hipStream_t)stream,
+                           (const float*)params, target_params, P, (float)hparams->tau);
+        HIP_TRY(hipGetLastError());
+    }
+    return FWG_OK;
+}
+
+int fwg_ddpg_step(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int64_t B, int64_t update, int policy_delay, const fwg_ddpg_hparams* hparams,
+                  float* params, float* target_params, float* adam_m, float* adam_v, int32_t* steps, float* stats_acc, void* stream) {
+    DDPG_NEED("fwg_ddpg_step", learner); DDPG_NEED("fwg_ddpg_step", hparams); DDPG_NEED("fwg_ddpg_step", params); DDPG_NEED("fwg_ddpg_step", target_params);
+    DDPG_NEED("fwg_ddpg_step", adam_m); DDPG_NEED("fwg_ddpg_step", adam_v); DDPG_NEED("fwg_ddpg_step", steps); DDPG_NEED("fwg_ddpg_step", stats_acc);
+    DDPG_BATCH("fwg_ddpg_step", batch, B);
+    if (update < 1) return fail_with(FWG_ERR_INVALID, "fwg_ddpg_step: update counts from 1, it is " + std::to_string((long long)update));
+    if (policy_delay < 1) return fail_with(FWG_ERR_INVALID, "fwg_ddpg_step: policy_delay must be positive, it is " + std::to_string(policy_delay));
+    float* g = learner->d_grad;
+    int rc = ddpg_launch_grad(learner, 1, batch, B, (float)hparams->gamma, params, target_params, g, nullptr, (hipStream_t)stream);
+    if (rc != FWG_OK) return rc;
+    rc = fwg_ddpg_apply(learner, FWG_DDPG_CRITICS, g, B, hparams, params, adam_m, adam_v, steps, stats_acc, nullptr, stream);
+    if (rc != FWG_OK || update % policy_delay != 0) return rc;
+    rc = ddpg_launch_grad(learner, 0, batch, B, 0.f, params, nullptr, g, nullptr, (hipStream_t)stream);
+    if (rc != FWG_OK) return rc;
+    return fwg_ddpg_apply(learner, FWG_DDPG_ACTOR, g, B, hparams, params, adam_m, adam_v, steps, stats_acc, target_params, stream);
 }
 
 }  // extern "C"

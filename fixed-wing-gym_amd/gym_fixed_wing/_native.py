@@ -184,6 +184,21 @@ STREAM_REPLAY = 11                                              # Philox stream 
 PPO_NSTAT = 4   # loss sums appended to a gradient buffer (include/fwgym.h "PPO update")
 
 
+class OffpolicyBatch(C.Structure):
+    """fwg_offpolicy_batch (include/fwgym.h "Off-policy update"): device pointers of one minibatch; goal rows have a stride of 4."""
+    _fields_ = [(n, C.c_void_p) for n in ["obs", "next_obs", "action", "goal_rows", "reward", "done"]]
+
+
+class DdpgHparams(C.Structure):
+    """fwg_ddpg_hparams: a host struct, read when a call is issued.  max_grad_norm_* <= 0: no clipping."""
+    _fields_ = [(n, C.c_double) for n in ["gamma", "tau", "lr_actor", "lr_critic", "beta1", "beta2", "eps", "max_grad_norm_actor",
+                                          "max_grad_norm_critic"]]
+
+
+DDPG_NSTAT = 4                      # loss sums appended to a gradient buffer (include/fwgym.h "Off-policy update")
+DDPG_ACTOR, DDPG_CRITICS = 0, 1     # FWG_DDPG_ACTOR / FWG_DDPG_CRITICS: the two segments of the flat parameter vector
+
+
 class NativeError(RuntimeError):
     pass
 
@@ -264,6 +279,14 @@ PROTOTYPES = {
     "fwg_ppo_apply": (_int, [_vp, _vp, _i64] + [_vp] * 7),
     "fwg_ppo_step": (_int, [_vp, C.POINTER(PpoBatch), _vp, _i64] + [_vp] * 8),
     "fwg_actor_pack": (_int, [_vp, _vp, _vp]),
+    "fwg_offpolicy_create": (_int, [_int, _int, _int, _int, C.POINTER(_vp)]),
+    "fwg_offpolicy_destroy": (None, [_vp]),
+    "fwg_offpolicy_num_params": (_i64, [_vp]),
+    "fwg_offpolicy_actor_params": (_i64, [_vp]),
+    "fwg_ddpg_critic_grad": (_int, [_vp, C.POINTER(OffpolicyBatch), _i64, C.POINTER(DdpgHparams)] + [_vp] * 5),
+    "fwg_ddpg_actor_grad": (_int, [_vp, C.POINTER(OffpolicyBatch), _i64, _vp, _vp, _vp]),
+    "fwg_ddpg_apply": (_int, [_vp, _int, _vp, _i64, C.POINTER(DdpgHparams)] + [_vp] * 7),
+    "fwg_ddpg_step": (_int, [_vp, C.POINTER(OffpolicyBatch), _i64, _i64, _int, C.POINTER(DdpgHparams)] + [_vp] * 7),
 }
 EXPORTS = list(PROTOTYPES)
 _libs = {}

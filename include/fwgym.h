@@ -839,6 +839,75 @@ int fwg_replay_sample(const fwg_handle* h, const fwg_goal_spec* spec, const fwg_
                       uint64_t seed, uint32_t serial, uint64_t p_scaled, float* obs_out, float* next_obs_out, float* action_out,
                       float* achieved_out, float* desired_out, float* reward_out, uint8_t* done_out, int32_t* index_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Off-policy update: what learns from the minibatches of fwg_replay_sample -- DDPG, or with two critics and a policy delay TD3's
+ * clipped double-Q and delayed actor step, as HIP kernels on the scheme of the PPO update (64-row tiles in LDS, bf16 matrix cores
+ * with every fp32 operand split hi + lo, one partial-gradient slab per workgroup summed in a fixed order: no float atomics, the
+ * update is bitwise deterministic run to run).  The exports are additions to ABI 26: no struct or call that existed changes.
+ *
+ * Sizes: D = obs_words, G = goal_words (1 .. 4), A = act_dim (1 .. 4); the actor reads [o | g] (D + G words), a critic [o | g | a]
+ * (D + G + A words), and D + G + A <= 64 (one 64-wide LDS tile holds a row).  Hidden layers 64-64 with ReLU:
+ *   pi(o, g)     = tanh(W3 relu(W2 relu(W1 [o | g] + b1) + b2) + b3)
+ *   Q_j(o, g, a) = w3 relu(W2 relu(W1 [o | g | a] + b1) + b2) + b3,   j < n_critics (1: DDPG, 2: TD3's twin critics)
+ * Online and target parameters are two flat float32 vectors with one layout, torch's parameters() order of
+ * nn.Sequential(Linear, ReLU, Linear, ReLU, Linear[, Tanh]):  actor | critic 0 | critic 1, each
+ *   W1 [64][K]  b1 [64]  W2 [64][64]  b2 [64]  W3 [nout][64]  b3 [nout]
+ * -- fwg_offpolicy_num_params() floats, the first fwg_offpolicy_actor_params() of them the actor's ("segment" FWG_DDPG_ACTOR; the
+ * rest is segment FWG_DDPG_CRITICS).  Adam's moments have the same layout.  A gradient buffer holds 4 more floats behind it, batch
+ * sums: sum_j sum (Q_j(o,g,a) - y)^2, sum Q_0(o,g,pi(o,g)), sum Q_0(o,g,a), sum y.
+ *
+ * Update u (counting from 1) on B rows (o, o', a, g, r, done):
+ *   critic step: a' = pi_target(o', g), q' = min_j Q_target,j(o', g, a'), y = r + gamma (1 - done) q' (no gradient through y; y is r
+ *     itself, bit for bit, on a row with done set and at gamma = 0), L_c = sum_j mean_B (Q_j(o,g,a) - y)^2, Adam on the critics;
+ *   if u % policy_delay == 0, the actor step with the critics as just updated: L_a = -mean_B Q_0(o, g, pi(o,g)), Adam on the actor
+ *     (the critics' gradient words are neither computed nor written), then theta_target <- lerp(theta_target, theta, tau) on everything.
+ * Adam is torch.optim.Adam's form; the bias corrections are computed from doubles.  max_grad_norm_* > 0 clips first, PER SEGMENT
+ * (clip_grad_norm_ over the segment's words): the actor's gradient by its own norm, the critics' by one joint norm over both
+ * critics -- they are one optimiser's parameters; <= 0: no clipping.  TD3's target-policy smoothing noise is not part of it.
+ *
+ * fwg_offpolicy_batch, device pointers: obs, next_obs [B][D], action [B][A], goal_rows [B][4] (row stride 4 words whatever G is:
+ * fwg_replay_sample's desired_out as it stands), reward [B], done uint8 [B].  fwg_ddpg_hparams is a HOST struct, read at the call.
+ * All launches go to the caller's stream; nothing synchronises or allocates after fwg_offpolicy_create (which allocates on the
+ * current device; it takes no env handle and no head).  A learner owns ONE set of partial-gradient slabs and one gradient buffer,
+ * which both gradient calls and fwg_ddpg_step reuse: it serves one stream at a time -- calls on one learner from two streams must be
+ * ordered by the caller (a learner per stream otherwise).
+ * Refused with FWG_ERR_INVALID and a message naming the argument (nothing is launched): a NULL pointer, B < 1, goal_words or act_dim
+ * outside 1 .. 4, n_critics outside {1, 2}, D + G + A > 64 (the message gives the three sizes), a segment other than 0 / 1,
+ * update < 1, policy_delay < 1.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fwg_offpolicy fwg_offpolicy;
+enum { FWG_DDPG_ACTOR = 0, FWG_DDPG_CRITICS = 1 };
+typedef struct fwg_offpolicy_batch {
+    const float* obs;
+    const float* next_obs;
+    const float* action;
+    const float* goal_rows;
+    const float* reward;
+    const uint8_t* done;
+} fwg_offpolicy_batch;
+typedef struct fwg_ddpg_hparams {
+    double gamma, tau, lr_actor, lr_critic, beta1, beta2, eps, max_grad_norm_actor, max_grad_norm_critic;
+} fwg_ddpg_hparams;
+int fwg_offpolicy_create(int obs_words, int goal_words, int act_dim, int n_critics, fwg_offpolicy** out);
+void fwg_offpolicy_destroy(fwg_offpolicy* learner);
+int64_t fwg_offpolicy_num_params(const fwg_offpolicy* learner);
+int64_t fwg_offpolicy_actor_params(const fwg_offpolicy* learner);
+/* The critics' segment of grad_out [P + 4] and the loss sums 0, 2, 3 (two launches: the gradient slabs, their reduction); the
+ * actor's segment and sum 1 are left as they are.  td_target_out: NULL, or [B] receives y. */
+int fwg_ddpg_critic_grad(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int64_t B, const fwg_ddpg_hparams* hparams, const float* params,
+                         const float* target_params, float* grad_out, float* td_target_out, void* stream);
+/* The actor's segment of grad_out and loss sum 1; the critics' segment and sums 0, 2, 3 are left as they are. */
+int fwg_ddpg_actor_grad(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int64_t B, const float* params, float* grad_out, void* stream);
+/* Adam on one segment of params / adam_m / adam_v with steps[segment] (int32 [2], on the device) as its step counter; stats_acc [4]
+ * (critic_loss, actor_loss, q_mean, target_mean) += that segment's statistics of the batch (critics: 0, 2, 3; actor: 1).  The other
+ * segment, its moments and its counter are not touched.  target_params: NULL, or the Polyak pass over the WHOLE vector follows. */
+int fwg_ddpg_apply(fwg_offpolicy* learner, int segment, const float* grad, int64_t B, const fwg_ddpg_hparams* hparams, float* params, float* adam_m,
+                   float* adam_v, int32_t* steps, float* stats_acc, float* target_params, void* stream);
+/* One whole update `update` (>= 1) into the learner's own gradient buffer: the critic step (three launches), and when
+ * update % policy_delay == 0 -- decided here, on the host -- the actor step and the Polyak pass (four more). */
+int fwg_ddpg_step(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int64_t B, int64_t update, int policy_delay, const fwg_ddpg_hparams* hparams,
+                  float* params, float* target_params, float* adam_m, float* adam_v, int32_t* steps, float* stats_acc, void* stream);
+
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);
 
