@@ -10,7 +10,8 @@ built for the host emulation only.  The eval_* mutants (the evaluation protocol 
 fwgym_eval.h) run tests/test_eval_device.py; the recorder_* mutants (the device flight recorder, fwgym_record.h) tests/test_recorder.py;
 the monitor_* mutants (the device training monitor, fwgym_monitor.h) the kernel tests of tests/test_monitor.py; the goal_* mutants
 (the goal env, fwgym_goal.h) the kernel tests of tests/test_goal.py; the replay_* mutants (the hindsight replay buffer, fwgym_replay.h)
-the kernel tests of tests/test_replay.py.
+the kernel tests of tests/test_replay.py; the ddpg_* mutants (the off-policy update, fwgym_offpolicy.h) the emulated forms of
+tests/test_offpolicy_contract.py.
 
     python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
@@ -196,6 +197,33 @@ MUTANTS = {
     # the slot drawn over the K allocated slots instead of the n_filled that hold a rollout
     "replay_slot_drawn_over_all_slots": [
         ("fwgym_replay.h", "        const long k = (long)__umulhi(a.x, A.n_filled);", "        const long k = (long)__umulhi(a.x, A.n_slots);")],
+    # ---- the off-policy update (fwgym_offpolicy.h), arithmetic only and in bounds: plausible slips of a rewrite for speed; they run
+    # the emulated forms of tests/test_offpolicy_contract.py.  With more tiles than workgroups every workgroup takes ntiles / gridDim.x
+    # tiles and the remainder is dropped (equal to the even split up to 256 tiles): in the critics' kernel ...
+    "ddpg_critic_grad_drops_remainder_tiles": [
+        ("fwgym_offpolicy.h", "t1 = (long)(blockIdx.x + 1) * G.ntiles / gridDim.x;\n    DdpgAcc g[2];",
+         "t1 = t0 + G.ntiles / gridDim.x;\n    DdpgAcc g[2];")],
+    # ... and in the actor's
+    "ddpg_actor_grad_drops_remainder_tiles": [
+        ("fwgym_offpolicy.h", "t1 = (long)(blockIdx.x + 1) * G.ntiles / gridDim.x;\n    DdpgAcc g, none;",
+         "t1 = t0 + G.ntiles / gridDim.x;\n    DdpgAcc g, none;")],
+    # the two learning rates swapped
+    "ddpg_apply_swaps_learning_rates": [
+        ("fwgym_offpolicy.h", "    const double lr = seg ? h.lr_critic : h.lr_actor;", "    const double lr = seg ? h.lr_actor : h.lr_critic;")],
+    # the two clip norms swapped
+    "ddpg_apply_swaps_clip_norms": [
+        ("fwgym_offpolicy.h", "    const float max_norm = (float)(seg ? h.max_norm_critic : h.max_norm_actor);",
+         "    const float max_norm = (float)(seg ? h.max_norm_actor : h.max_norm_critic);")],
+    # the fourth word of a goal row never read (every goal the env makes today has three)
+    "ddpg_gather_drops_goal_word_3": [
+        ("fwgym_offpolicy.h", "            else if (f < L.Ka) v = goal[row * FWG_DDPG_GOAL_STRIDE + f - L.D];",
+         "            else if (f < L.Ka) v = f - L.D < 3 ? goal[row * FWG_DDPG_GOAL_STRIDE + f - L.D] : 0.f;")],
+    # the actor's step counter in both segments' bias correction (and written back to the segment's own)
+    "ddpg_apply_bias_correction_of_step_0": [
+        ("fwgym_offpolicy.h", "    const int t = step[seg] + 1;", "    const int t = step[0] + 1;")],
+    # the first layer's weight gradient without its columns 32 .. 63
+    "ddpg_backward_skips_w1_columns_from_32": [
+        ("fwgym_offpolicy.h", "        if (tn0 < K) ppo_mma_tile<true>(g.w1,", "        if (tn0 < K && tn0 < 32) ppo_mma_tile<true>(g.w1,")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -211,7 +239,8 @@ _MONITOR_TESTS = ["-k", "restatement or bad_reward or carries or sharded", os.pa
 _REPLAY_TESTS = ["-k", "restatement or seed_and_serial or backward_scan", os.path.join(ROOT, "tests", "test_replay.py")]
 _GOAL_TESTS = ["-k", "matches_the_restatement or golden or own_goals or sharded", os.path.join(ROOT, "tests", "test_goal.py")]
 _HEAD_CNN_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract_cnn.py")]
-TESTS = {name: (_REPLAY_TESTS if name.startswith("replay_") else _GOAL_TESTS if name.startswith("goal_") else _MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+_OFFPOLICY_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_offpolicy_contract.py")]
+TESTS = {name: (_OFFPOLICY_TESTS if name.startswith("ddpg_") else _REPLAY_TESTS if name.startswith("replay_") else _GOAL_TESTS if name.startswith("goal_") else _MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
