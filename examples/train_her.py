@@ -53,7 +53,13 @@ def main():
     ap.add_argument("--update", default="torch", choices=["torch", "hip"], help="the update path: torch autograd, or the HIP kernels")
     ap.add_argument("--twin", action="store_true", help="two critics, the target takes the smaller value (TD3's clipped double-Q)")
     ap.add_argument("--policy-delay", type=int, default=1, help="critic updates per actor update (TD3: 2)")
+    ap.add_argument("--collect", default="torch", choices=["torch", "device"],
+                    help="the behaviour rollout: the torch loop below, or gym_fixed_wing.behaviour.HindsightCollector (one HIP launch per act)")
+    ap.add_argument("--graph", action="store_true", help="--collect device: capture the rollout once and replay it (--n-steps must be even)")
+    ap.add_argument("--random-eps", type=float, default=0.0, help="--collect device: probability of a uniform random action per env and step")
     args = ap.parse_args()
+    if args.graph and args.collect != "device":
+        ap.error("--graph needs --collect device")
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     vec = FixedWingVecEnv(her_config(), num_envs=args.envs, device=0, seed=0)
@@ -68,17 +74,27 @@ def main():
     actions, raw = torch.zeros((T, N, 3), device=dev), torch.zeros((T, N), device=dev)
     dones = torch.zeros((T, N), dtype=torch.uint8, device=dev)
     cur = env.reset()
+    collector = None
+    if args.collect == "device":   # the same rollout as 2 T + 1 launches (with --graph: one replayed graph)
+        from gym_fixed_wing.behaviour import HindsightCollector
+        collector = HindsightCollector(vec, agent, T, graph=args.graph, seed=0, noise=args.noise, random_eps=args.random_eps)
+        log, raw = collector.goals, collector.buf["raw_rewards"]
     batch = None
     for it in range(args.iters):
-        log.observe(0)
-        for t in range(T):
-            a = agent.act(cur["observation"].reshape(N, D), cur["desired_goal"], noise=args.noise)
-            obs[t].copy_(cur["observation"].reshape(N, D))
-            actions[t].copy_(a)
-            cur, _, d = env.step_device(actions[t], reward_out=raw[t])
-            dones[t].copy_(d)
-            log.observe(t + 1)
-        replay.add(obs, cur["observation"].reshape(N, D), actions, raw, dones, log)
+        if collector is not None:
+            collector.head.refresh()   # (--update torch: the head acts on a copy of the actor's weights)
+            collector.run()
+            replay.add_rollout(collector)
+        else:
+            log.observe(0)
+            for t in range(T):
+                a = agent.act(cur["observation"].reshape(N, D), cur["desired_goal"], noise=args.noise)
+                obs[t].copy_(cur["observation"].reshape(N, D))
+                actions[t].copy_(a)
+                cur, _, d = env.step_device(actions[t], reward_out=raw[t])
+                dones[t].copy_(d)
+                log.observe(t + 1)
+            replay.add(obs, cur["observation"].reshape(N, D), actions, raw, dones, log)
         # the final distance to the goal of the rollout's last row, in scaled units
         miss = (log.achieved[T, :, :G] - log.desired[T, :, :G]).abs().mean(dim=0)
         stats = {"critic_loss": 0.0, "actor_loss": 0.0}

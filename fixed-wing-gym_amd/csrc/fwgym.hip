@@ -25,6 +25,7 @@
 #include "fwgym_goal.h"    // the goal-conditioned view and hindsight relabelling (fwg_goal_observe, fwg_goal_reward, fwg_goal_relabel)
 #include "fwgym_replay.h"  // the hindsight replay buffer: episode index and relabelling at sample time (fwg_replay_index, fwg_replay_sample)
 #include "fwgym_monitor.h" // the device training monitor (fwg_monitor_fold, fwg_monitor_take)
+#include "fwgym_behaviour.h" // the behaviour policy of an off-policy learner as one launch (fwg_behaviour_act)
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
@@ -3357,6 +3358,64 @@ int fwg_ddpg_step(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int6
     rc = ddpg_launch_grad(learner, 0, batch, B, 0.f, params, nullptr, g, nullptr, (hipStream_t)stream);
     if (rc != FWG_OK) return rc;
     return fwg_ddpg_apply(learner, FWG_DDPG_ACTOR, g, B, hparams, params, adam_m, adam_v, steps, stats_acc, target_params, stream);
+}
+
+}  // extern "C"
+
+// =====================================================================================================================
+// Behaviour head (include/fwgym.h "Behaviour head"): kernel in fwgym_behaviour.h
+// =====================================================================================================================
+extern "C" {
+
+int fwg_behaviour_act(const fwg_handle* env, const fwg_goal_spec* goal_spec, int64_t N, int D, int G, int A, const float* params, const float* obs,
+                      const float* goal_rows, float* achieved_out, float* desired_out, float* obs_out, float* action_out, const uint8_t* done_in,
+                      uint8_t* done_out, uint32_t* draws, const uint32_t* noise_params, uint64_t seed, uint32_t env_id_base, int deterministic,
+                      void* stream) {
+    const std::string sizes = " (D " + std::to_string(D) + ", G " + std::to_string(G) + ", A " + std::to_string(A) + ")";
+    if (D < 1) return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: D must be positive" + sizes);
+    if (G < 1 || G > 4) return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: G must be in 1 .. 4" + sizes);
+    if (A < 1 || A > 4) return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: A must be in 1 .. 4" + sizes);
+    if ((long)D + G > 64)
+        return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: the actor's input width D + G = " + std::to_string((long)D + G) + " exceeds 64, one LDS tile row" + sizes);
+    if ((long)D + G + A > 64)
+        return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: the critic's input width D + G + A = " + std::to_string((long)D + G + A) +
+                         " exceeds 64: no off-policy learner has this layout" + sizes);
+    if ((env != nullptr) == (goal_rows != nullptr))
+        return fail_with(FWG_ERR_INVALID, env ? "fwg_behaviour_act: both env and goal_rows are given: the goal rows come from one of them"
+                                              : "fwg_behaviour_act: neither env nor goal_rows is given: the goal rows come from one of them");
+    DDPG_NEED("fwg_behaviour_act", params); DDPG_NEED("fwg_behaviour_act", obs); DDPG_NEED("fwg_behaviour_act", action_out);
+    DDPG_NEED("fwg_behaviour_act", draws); DDPG_NEED("fwg_behaviour_act", noise_params);
+    if ((done_in != nullptr) != (done_out != nullptr))
+        return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: done_in and done_out go together");
+    BehaviourArgs B = {};
+    if (env) {
+        if (env->h.obs_log != 0)
+            return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: env writes a row log (obs_log_rows " + std::to_string(env->h.obs_log) +
+                             "): the head reads the dense observation batch");
+        DDPG_NEED("fwg_behaviour_act", goal_spec); DDPG_NEED("fwg_behaviour_act", achieved_out); DDPG_NEED("fwg_behaviour_act", desired_out);
+        if (const int st = goal_lower("fwg_behaviour_act", env, goal_spec, false, false, &B.g)) return st;
+        if (N != env->n_envs)
+            return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: N is " + std::to_string((long long)N) + ", env has " + std::to_string((long long)env->n_envs) + " envs");
+        if (G != goal_spec->n_goals)
+            return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: G is " + std::to_string(G) + ", goal_spec has " + std::to_string(goal_spec->n_goals) + " goals");
+        if (D != env->h.obs_dim)
+            return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: D is " + std::to_string(D) + ", env's observation has " + std::to_string(env->h.obs_dim) + " words");
+        const fwg_layout& Ly = env->h.L;
+        B.rc = {Ly.sim, Ly.cold, Ly.derived, Ly.gym, env->h.store_derived, env->h.turbulence, env->h.auto_reset};
+        B.S = (const float*)env->arena;
+    }
+    if (N < 1 || (N + FWG_PPO_ROWS - 1) / FWG_PPO_ROWS > 0x7fffffff)
+        return fail_with(FWG_ERR_INVALID, "fwg_behaviour_act: N must be positive and within one grid, it is " + std::to_string((long long)N));
+    B.N = (long)N;
+    B.L = ddpg_layout(D, G, A, 1);
+    B.params = params; B.obs = obs; B.goal_rows = goal_rows;
+    B.achieved_out = (float4*)achieved_out; B.desired_out = (float4*)desired_out; B.obs_out = obs_out; B.action_out = action_out;
+    B.done_in = done_in; B.done_out = done_out; B.draws = draws; B.noise_params = noise_params;
+    B.seed_lo = (unsigned)seed; B.seed_hi = (unsigned)(seed >> 32); B.env_id_base = env_id_base; B.deterministic = deterministic ? 1 : 0;
+    hipLaunchKernelGGL(k_behaviour_act, dim3((unsigned)((N + FWG_PPO_ROWS - 1) / FWG_PPO_ROWS)), dim3(FWG_PPO_THREADS),
+                       (size_t)behaviour_lds_floats() * sizeof(float), (hipStream_t)stream, B);
+    HIP_TRY(hipGetLastError());
+    return FWG_OK;
 }
 
 }  // extern "C"

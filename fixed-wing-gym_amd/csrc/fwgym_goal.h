@@ -161,11 +161,9 @@ __device__ __forceinline__ float goal_reward(const DevCfg& c, const GoalCfg& g, 
     return reward;
 }
 
-// one lane per env: the goal rows of the committed state and the current targets
-__global__ __launch_bounds__(256) void k_goal_observe(RecCfg rc, GoalCfg g, const float* __restrict__ S, long N, float4* __restrict__ achieved,
-                                                      float4* __restrict__ desired) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= N) return;
+// the goal rows of env e: the committed state and the current targets (k_goal_observe, and the behaviour head of fwgym_behaviour.h)
+__device__ __forceinline__ void goal_rows_of(const RecCfg& rc, const GoalCfg& g, const float* __restrict__ S, long N, long e, float4& achieved,
+                                             float4& desired) {
     float a[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -174,8 +172,19 @@ __global__ __launch_bounds__(256) void k_goal_observe(RecCfg rc, GoalCfg g, cons
             d[i] = (rec_arena(S, N, e, rc.gym + g.k[i]) - g.mean[i]) / g.var[i];
         }
     }
-    achieved[e] = make_float4(a[0], a[1], a[2], rec_arena(S, N, e, rc.gym + 3));   // word 3: the step word, as bits
-    desired[e] = make_float4(d[0], d[1], d[2], 0.f);
+    achieved = make_float4(a[0], a[1], a[2], rec_arena(S, N, e, rc.gym + 3));   // word 3: the step word, as bits
+    desired = make_float4(d[0], d[1], d[2], 0.f);
+}
+
+// one lane per env
+__global__ __launch_bounds__(256) void k_goal_observe(RecCfg rc, GoalCfg g, const float* __restrict__ S, long N, float4* __restrict__ achieved,
+                                                      float4* __restrict__ desired) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= N) return;
+    float4 a, d;
+    goal_rows_of(rc, g, S, N, e, a, d);
+    achieved[e] = a;
+    desired[e] = d;
 }
 
 // one lane per transition: act_win [W][m] rows (a0 a1 a2 -), row W - 1 the transition's own action

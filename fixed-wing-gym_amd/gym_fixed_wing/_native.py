@@ -197,6 +197,8 @@ class DdpgHparams(C.Structure):
 
 DDPG_NSTAT = 4                      # loss sums appended to a gradient buffer (include/fwgym.h "Off-policy update")
 DDPG_ACTOR, DDPG_CRITICS = 0, 1     # FWG_DDPG_ACTOR / FWG_DDPG_CRITICS: the two segments of the flat parameter vector
+STREAM_BEHAVIOUR = 12               # Philox stream of the behaviour head's exploration draws
+BEHAVIOUR_NOISE_WORDS = 4           # fwg_behaviour_act's noise_params: sigma (float bits), eps_scaled low / high word, 0
 
 
 class NativeError(RuntimeError):
@@ -287,6 +289,7 @@ PROTOTYPES = {
     "fwg_ddpg_actor_grad": (_int, [_vp, C.POINTER(OffpolicyBatch), _i64, _vp, _vp, _vp]),
     "fwg_ddpg_apply": (_int, [_vp, _int, _vp, _i64, C.POINTER(DdpgHparams)] + [_vp] * 7),
     "fwg_ddpg_step": (_int, [_vp, C.POINTER(OffpolicyBatch), _i64, _i64, _int, C.POINTER(DdpgHparams)] + [_vp] * 7),
+    "fwg_behaviour_act": (_int, [_vp, C.POINTER(GoalSpecStruct), _i64, _int, _int, _int] + [_vp] * 11 + [_u64, C.c_uint32, _int, _vp]),
 }
 EXPORTS = list(PROTOTYPES)
 _libs = {}

@@ -908,6 +908,37 @@ int fwg_ddpg_apply(fwg_offpolicy* learner, int segment, const float* grad, int64
 int fwg_ddpg_step(fwg_offpolicy* learner, const fwg_offpolicy_batch* batch, int64_t B, int64_t update, int policy_delay, const fwg_ddpg_hparams* hparams,
                   float* params, float* target_params, float* adam_m, float* adam_v, int32_t* steps, float* stats_acc, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Behaviour head: the behaviour policy of an off-policy learner between two env steps of an exploration rollout, as ONE launch
+ * (one workgroup per 64 envs).  An addition to ABI 26: no struct or call that existed changes.
+ *
+ * Sizes as in "Off-policy update": D observation words, G goal words (1 .. 4), A actions (1 .. 4), D + G + A <= 64.  params: device
+ * pointer to the actor's parameters, flat fp32 in the actor's layout there (W1 [64][D + G] b1 W2 b2 W3 [A][64] b3) -- the first
+ * fwg_offpolicy_actor_params words of a learner's online vector, read in place at every launch.
+ *
+ * Per env e < N, in this order:
+ *   goal rows    env given: achieved_out[e] / desired_out[e] ([N][4]) = what fwg_goal_observe writes for the env's state, bit for
+ *                bit; the actor's goal is desired_out[e][0 .. G).  No env: goal_rows[e][0 .. G) as given ([N][4]).
+ *   obs_out      NULL, or [N][D] receives obs[e] (the rollout's observation row: no copy launch)
+ *   pi           tanh(actor([obs[e] | goal]))
+ *   exploration  unless `deterministic`: c = draws[e] (uint32 [N], device), draws[e] = c + 1 -- no counter travels by value, so a
+ *                captured launch replays correctly.  Philox blocks philox4x32(env_id_base + e, c, sub, 12, seed lo, seed hi) (12:
+ *                the stream of these draws): sub 0 -> normals n_0 .. n_3 by Box-Muller; sub 1 -> uniforms u_i = 2 u01(x_i) - 1;
+ *                sub 2, word 0 < eps_scaled -> the action is (u_0 .. u_{A-1}), else clamp(pi_i + sigma n_i, -1, 1).
+ *                noise_params (uint32 [4], device): sigma as float bits, eps_scaled = min(2^32, round(eps 2^32)) as low word and
+ *                high word, 0.  `deterministic` neither reads nor writes draws or noise_params.
+ *   stores       action_out[e][0 .. A); done_out[e] = done_in[e] when both are given (uint8 [N]; both or neither).
+ * The launch goes to `stream`; nothing synchronises or allocates.
+ * Refused with FWG_ERR_INVALID and a message naming the argument (nothing is launched): D + G > 64, D + G + A > 64 (the message
+ * gives the three sizes), G or A outside 1 .. 4, both or neither of env / goal_rows, an env that writes a row log (obs_log_rows
+ * != 0), N / D / G that are not the env's, a NULL required pointer (params, obs, action_out, draws, noise_params; with an env
+ * goal_spec, achieved_out, desired_out), N < 1.
+ * ------------------------------------------------------------------------------------------------------------------ */
+int fwg_behaviour_act(const fwg_handle* env, const fwg_goal_spec* goal_spec, int64_t N, int D, int G, int A, const float* params, const float* obs,
+                      const float* goal_rows, float* achieved_out, float* desired_out, float* obs_out, float* action_out, const uint8_t* done_in,
+                      uint8_t* done_out, uint32_t* draws, const uint32_t* noise_params, uint64_t seed, uint32_t env_id_base, int deterministic,
+                      void* stream);
+
 /* Global step counter driving the ring slots (diagnostics/tests). */
 int64_t fwg_global_step(const fwg_handle* h);
 

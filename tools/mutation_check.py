@@ -11,9 +11,10 @@ fwgym_eval.h) run tests/test_eval_device.py; the recorder_* mutants (the device 
 the monitor_* mutants (the device training monitor, fwgym_monitor.h) the kernel tests of tests/test_monitor.py; the goal_* mutants
 (the goal env, fwgym_goal.h) the kernel tests of tests/test_goal.py; the replay_* mutants (the hindsight replay buffer, fwgym_replay.h)
 the kernel tests of tests/test_replay.py; the ddpg_* mutants (the off-policy update, fwgym_offpolicy.h) the emulated forms of
-tests/test_offpolicy_contract.py.
+tests/test_offpolicy_contract.py; the behaviour_* mutants (the behaviour head, fwgym_behaviour.h) the emulated forms of
+tests/test_behaviour.py.
 
-    python tools/mutation_check.py emu [NAME ...]      # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
+    python tools/mutation_check.py emu [NAME ...]     # host emulation: each mutant (or the NAMEd) against its own tests (TESTS)
     python tools/mutation_check.py hip OUTDIR          # gfx950 libraries of the mutants (tools/devlib.py), for a GPU session:
                                                        # FWGYM_MUTANT_LIB_ROW_LOG=... python -m pytest tests/test_gpu_oracle_coverage.py
 
@@ -224,6 +225,13 @@ MUTANTS = {
     # the first layer's weight gradient without its columns 32 .. 63
     "ddpg_backward_skips_w1_columns_from_32": [
         ("fwgym_offpolicy.h", "        if (tn0 < K) ppo_mma_tile<true>(g.w1,", "        if (tn0 < K && tn0 < 32) ppo_mma_tile<true>(g.w1,")],
+    # ---- the behaviour head (fwgym_behaviour.h); they run the emulated forms of tests/test_behaviour.py.  The per-env draw counter
+    # read but not advanced: every act repeats the first one's noise
+    "behaviour_draw_counter_not_advanced": [
+        ("fwgym_behaviour.h", "        B.draws[e] = c + 1u;", "        B.draws[e] = c;")],
+    # the goal columns gathered one word off (in bounds for the goal widths the tests use, G <= 3: word 3 of a row is the last read)
+    "behaviour_goal_columns_one_word_off": [
+        ("fwgym_behaviour.h", "    ddpg_gather(Xs, L, B.obs, goal, nullptr, r0, nrows, tid);", "    ddpg_gather(Xs, L, B.obs, goal + 1, nullptr, r0, nrows, tid);")],
 }
 _ORACLE_TESTS = ["-k", "not frozen_kernel_through", os.path.join(ROOT, "tests", "test_emu_coverage.py"),
                  os.path.join(ROOT, "tests", "test_emu_fuzz.py")]
@@ -240,7 +248,8 @@ _REPLAY_TESTS = ["-k", "restatement or seed_and_serial or backward_scan", os.pat
 _GOAL_TESTS = ["-k", "matches_the_restatement or golden or own_goals or sharded", os.path.join(ROOT, "tests", "test_goal.py")]
 _HEAD_CNN_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_actor_contract_cnn.py")]
 _OFFPOLICY_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_offpolicy_contract.py")]
-TESTS = {name: (_OFFPOLICY_TESTS if name.startswith("ddpg_") else _REPLAY_TESTS if name.startswith("replay_") else _GOAL_TESTS if name.startswith("goal_") else _MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
+_BEHAVIOUR_TESTS = ["-m", "not gpu", os.path.join(ROOT, "tests", "test_behaviour.py")]
+TESTS = {name: (_BEHAVIOUR_TESTS if name.startswith("behaviour_") else _OFFPOLICY_TESTS if name.startswith("ddpg_") else _REPLAY_TESTS if name.startswith("replay_") else _GOAL_TESTS if name.startswith("goal_") else _MONITOR_TESTS if name.startswith("monitor_") else _RECORDER_TESTS if name.startswith("recorder_") else _EVAL_TESTS if name.startswith("eval_") else _HEAD_CNN_TESTS if name.startswith("head_cnn_") else _CNN_LEARNER_TESTS if name.startswith("ppo_cnn_") else _LEARNER_TESTS if name.startswith(("ppo_", "actor_pack_")) else _HEAD_TESTS if name.startswith("head_") else
                 _CURRICULUM_TESTS if name.endswith("_generation") else _ORACLE_TESTS) for name in MUTANTS}
 # (a level change moves no range the per-env sets are drawn from: a kept set equals a new draw, and only the seed change shows this one)
 TESTS["model_draw_ignores_generation"] = ["-k", "another_seed", os.path.join(ROOT, "tests", "test_emu_curriculum.py")]
